@@ -31,7 +31,13 @@ reads on N GPUs (strong scaling), DESIGN.md §6:
 GPU (replicated / bucket: each rank timed alone, step = slowest rank;
 exchange: buffers exchanged on the device).
 
-Prints ONE JSON line (rank 0).  See DESIGN.md §5 for the roofline numbers.
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line
+(rank 0): metric / value / ms_per_step, the steps' device times and the
+roofline figures they give.  --dump-outputs DIR also writes the last step's
+outputs (dump_outputs below).  --full adds every measurement that takes runs
+of its own: the counting pass (counters), the parity digests against
+tests/golden, the rows' D2H, the one-shot and device-ingest timings, the CPU
+baseline and --replay.  See DESIGN.md §5 for the roofline numbers.
 """
 from __future__ import annotations
 
@@ -384,6 +390,54 @@ def load_pmc(path, lib_sha=None):
     return (tot or None), f"{os.path.basename(path)} (library {prov})"
 
 
+DUMP_SEED = 20240531      # fixes which reads --dump-outputs samples
+DUMP_MAX_ROWS = 1_500_000  # x 4 float64 columns = 48 MB
+DUMP_MAX_SUPER = 500_000  # x 2 float64 columns = 8 MB
+
+
+def dump_outputs(out_dir, e, n_rows, n_reads, mixed_lengths):
+    """--dump-outputs: what the last timed step left, as float64 .npy files
+    (<= 64 MB in all), the same from run to run and comparable between builds:
+
+    n_rows.npy        [1]     the directed row count mg_find_overlaps returned
+    rows_sample.npy   [m, 4]  (src, dst, orient, offset) of the last step's rows
+                              (mg_copy_rows) whose src is one of a seeded sample
+                              of the read IDs, in canonical order (the device
+                              leaves the multiset in any order); every row when
+                              they fit, else at most DUMP_MAX_ROWS
+    super_sample.npy  [s, 2]  (read ID, superReadID) for a seeded sample of the
+                              read IDs (every ID when they fit)
+
+    The read sample depends only on DUMP_SEED, the number of unique reads and
+    the row count.  The timed step keeps the superReadIDs on the device
+    (mark_contained(copy=False)); they reach the host through one more
+    mg_mark_contained on the same index (mixed read lengths only: with one read
+    length they are all 0 and no containment pass runs)."""
+    from metagenomics_amd.overlap import sort_rows
+
+    os.makedirs(out_dir, exist_ok=True)
+    t0 = time.time()
+    rows = e.rows(n_rows)
+    assert rows.shape[0] == n_rows, (rows.shape[0], n_rows)
+    rng = np.random.default_rng(DUMP_SEED)
+    pri = rng.random(n_reads + 1, dtype=np.float32)  # one priority per read ID
+    if n_rows > DUMP_MAX_ROWS:
+        rows = rows[(pri < 0.9 * DUMP_MAX_ROWS / n_rows)[rows["src"]]]
+    rows = sort_rows(rows)[:DUMP_MAX_ROWS]
+    sample = np.stack([rows[f].astype(np.float64) for f in ("src", "dst", "orient", "offset")], axis=1)
+    del rows
+    sup = e.mark_contained(copy=True) if mixed_lengths else np.zeros(n_reads + 1, dtype=np.uint32)
+    ids = np.arange(1, n_reads + 1)
+    if n_reads > DUMP_MAX_SUPER:
+        ids = (np.flatnonzero(pri[1:] < 0.9 * DUMP_MAX_SUPER / n_reads) + 1)[:DUMP_MAX_SUPER]
+    files = {"n_rows": np.array([n_rows], dtype=np.float64), "rows_sample": sample,
+             "super_sample": np.stack([ids.astype(np.float64), sup[ids].astype(np.float64)], axis=1)}
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"[bench] --dump-outputs: {sum(a.nbytes for a in files.values()) / 1e6:.1f} MB in {time.time() - t0:.1f}s")
+    return {name: list(a.shape) for name, a in files.items()}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -419,7 +473,18 @@ def main():
                     help="skip the per-dataset one-shot timing (layout + one step, and ID order + one step)")
     ap.add_argument("--opt", action="append", default=[],
                     help="engine option NAME=VALUE (mg_set_option), repeatable; diagnostics / A-B runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline figure: the counting pass "
+                         "(counters), the parity digests against the golden, the rows' D2H timing, the one-shot "
+                         "timing, the device ingest, the CPU baseline and --replay (each with its own --no-* "
+                         "switch); without it the run sets up, warms up, times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step left (n_rows, a seeded sample of the rows "
+                         "in canonical order, a seeded sample of the superReadIDs) as DIR/<name>.npy "
+                         "(1 GPU, fused path)")
     args = ap.parse_args()
+    if args.replay and not args.full:
+        ap.error("--replay is one of the --full measurements: pass --full with it")
     # stdout carries exactly one JSON line: native libraries (RCCL prints its
     # version banner at communicator creation) write to fd 1, so fd 1 goes to
     # stderr for the whole run and the JSON line to a duplicate of the original
@@ -484,6 +549,8 @@ def main():
     else:
         mode = "fused"
     P = world if mode in ("exchange", "replicated", "bucket") else max(1, args.sim_world)
+    if args.dump_outputs and mode != "fused":
+        ap.error("--dump-outputs writes the 1-GPU fused path's outputs (no --sim-world, --exchange or several ranks)")
 
     from metagenomics_amd.sharded import sharded_step, source_range
 
@@ -552,16 +619,18 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(local)
 
-    # one counting pass (untimed) for the roofline's algorithmic bytes
-    for e in engines:
-        e.set_option("stats", 1)
-    rows = step()
-    cnt = {}
-    for e in engines:
-        for kk, v in e.counters().items():
-            cnt[kk] = cnt.get(kk, 0) + v
-        e.set_option("stats", 0)
-    cnt["sources"] = N if mode != "exchange" else cnt.get("sources", 0)
+    # --full: one counting pass (untimed) for the result line's work counters
+    cnt = None
+    if args.full:
+        for e in engines:
+            e.set_option("stats", 1)
+        rows = step()
+        cnt = {}
+        for e in engines:
+            for kk, v in e.counters().items():
+                cnt[kk] = cnt.get(kk, 0) + v
+            e.set_option("stats", 0)
+        cnt["sources"] = N if mode != "exchange" else cnt.get("sources", 0)
     for _ in range(args.warmup):
         step()
 
@@ -599,8 +668,8 @@ def main():
         rows = int(ee.item())
     edges = rows // 2
     # parity at the bench's own size: device digests of the last step vs the
-    # reference's digests of the same workload (outside the timed region)
-    parity = parity_digest(engines, last_res[0], mode, dist, args.config)
+    # reference's digests of the same workload (outside the timed region; --full)
+    parity = parity_digest(engines, last_res[0], mode, dist, args.config) if args.full else None
     if rank != 0:
         dist.barrier()
         dist.destroy_process_group()
@@ -702,7 +771,7 @@ def main():
     }
     if sim_rank_ms is not None:
         res["sim_rank_ms"] = sim_rank_ms
-    if world == 1 and mode == "fused" and not args.no_d2h:
+    if args.full and world == 1 and mode == "fused" and not args.no_d2h:
         try:
             d2h = d2h_rows(engines[0], rows)
             res["d2h_rows"] = d2h
@@ -711,7 +780,9 @@ def main():
             res["edges_per_sec_with_d2h"] = edges / ((ms_step + d2h["pinned_ms"]) / 1000.0)
         except Exception as e:  # report, never fake
             res["d2h_rows"] = {"error": str(e)}
-    if world == 1 and mode == "fused" and not args.no_one_shot:
+    if args.dump_outputs:
+        res["dumped_outputs"] = dump_outputs(args.dump_outputs, engines[0], rows, N, lo != hi)
+    if args.full and world == 1 and mode == "fused" and not args.no_one_shot:
         try:
             res["one_shot"] = one_shot(engines[0], ds, fused_step, local, rows)
             res["layout_ms"] = res["one_shot"]["layout_ms"]
@@ -719,7 +790,7 @@ def main():
             res["one_shot_edges_per_sec"] = edges / (res["one_shot"]["one_shot_ms"] / 1000.0)
         except Exception as e:  # report, never fake
             res["one_shot"] = {"error": str(e)}
-    if world == 1 and mode == "fused" and args.replay:
+    if args.full and world == 1 and mode == "fused" and args.replay:
         from metagenomics_amd.overlap import UnitigGraph
 
         t0 = time.perf_counter()
@@ -732,7 +803,7 @@ def main():
                                "contract_iterations": ug.iterations, "threads": 1}
         ug.close()
         del allrows
-    if world == 1 and mode == "fused" and not args.no_ingest:
+    if args.full and world == 1 and mode == "fused" and not args.no_ingest:
         try:
             res["dataset_ingest"] = device_ingest(ds, codes, lens, l, k, local, host_ingest_s, nthreads, rows)
             di = res["dataset_ingest"]
@@ -742,7 +813,7 @@ def main():
             res["one_shot_after_device_ingest_edges_per_sec"] = edges / (di["first_step_ms"] / 1000.0)
         except Exception as e:  # report, never fake
             res["dataset_ingest"] = {"error": str(e)}
-    if world == 1 and mode == "fused" and not args.no_cpu_baseline:
+    if args.full and world == 1 and mode == "fused" and not args.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline(cfg, args.cpu_sample, not args.no_cpu_full)
         except Exception as e:  # report, never fake

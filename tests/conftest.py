@@ -3,6 +3,7 @@ import json
 import os
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -40,7 +41,8 @@ def fixture_input(name, tmp_path_factory=None):
     """Decompress the fixture's input into a temp file; returns its path."""
     meta = load_meta(name)
     src = os.path.join(GOLDEN, meta["input"])
-    d = os.environ.get("MG_TEST_TMP") or "/tmp/mg_golden"
+    # (per user: a directory another account left behind is not writable)
+    d = os.environ.get("MG_TEST_TMP") or os.path.join(tempfile.gettempdir(), "mg_golden_%d" % os.getuid())
     os.makedirs(d, exist_ok=True)
     dst = os.path.join(d, meta["input"][:-3])
     if not os.path.exists(dst):

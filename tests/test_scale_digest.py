@@ -310,7 +310,7 @@ def test_exchange_two_processes(name):
     env = dict(os.environ, MG_BENCH_PG_BACKEND="gloo")
     args = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
             "--master-addr", "127.0.0.1", "--master-port", "29733", os.path.join(ROOT, "bench.py"),
-            "--gpus", "2", "--config", name, "--multi", "exchange", "--steps", "1", "--warmup", "1",
+            "--full", "--gpus", "2", "--config", name, "--multi", "exchange", "--steps", "1", "--warmup", "1",
             "--no-cpu-baseline", "--no-ingest"]
     out = subprocess.run(args, capture_output=True, text=True, timeout=800, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -337,7 +337,8 @@ def test_two_processes_default_mode(name, mode):
     env = dict(os.environ, MG_BENCH_PG_BACKEND="gloo")
     args = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
             "--master-addr", "127.0.0.1", "--master-port", "29735", os.path.join(ROOT, "bench.py"),
-            "--gpus", "2", "--config", name, "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-ingest"]
+            "--full", "--gpus", "2", "--config", name, "--steps", "1", "--warmup", "1", "--no-cpu-baseline",
+            "--no-ingest"]
     out = subprocess.run(args, capture_output=True, text=True, timeout=800, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
@@ -362,7 +363,7 @@ def test_two_processes_no_collective_modes(mode, desc):
     env = dict(os.environ, MG_BENCH_PG_BACKEND="gloo")
     args = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
             "--master-addr", "127.0.0.1", "--master-port", "29737", os.path.join(ROOT, "bench.py"),
-            "--gpus", "2", "--config", "c2", "--multi", mode, "--steps", "1", "--warmup", "1",
+            "--full", "--gpus", "2", "--config", "c2", "--multi", mode, "--steps", "1", "--warmup", "1",
             "--no-cpu-baseline", "--no-ingest"]
     out = subprocess.run(args, capture_output=True, text=True, timeout=800, env=env)
     assert out.returncode == 0, out.stderr[-3000:]

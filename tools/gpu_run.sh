@@ -19,25 +19,25 @@ for s in $STEPS; do
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
     rc=$?; echo "smoke rc=$rc"; tail -3 $OUT/smoke.log ;;
   bench)
-    timeout -k 10 600 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err
+    timeout -k 10 600 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err
     rc=$?; echo "bench rc=$rc"; cat $OUT/bench.json ;;
   sim)
     for P in 2 4 8; do
-      timeout -k 10 300 python -u bench.py --sim-world $P --multi exchange --steps 3 --no-cpu-baseline --no-ingest > $OUT/bench_sim$P.json 2> $OUT/bench_sim$P.err
+      timeout -k 10 300 python -u bench.py --full --sim-world $P --multi exchange --steps 3 --no-cpu-baseline --no-ingest > $OUT/bench_sim$P.json 2> $OUT/bench_sim$P.err
       rc=$?; echo "bench sim $P rc=$rc"; python3 -c "import json;d=json.load(open('$OUT/bench_sim$P.json'));print('ms/step',round(d['ms_per_step'],3),'digest_ok',d['parity'].get('digest_ok'),'reruns',d.get('exchange_reruns'),d.get('phase_wall_ms'))"; [ $rc -ne 0 ] && break
     done ;;
   simrep)
     for P in 2 4 8; do
-      timeout -k 10 600 python -u bench.py --config ${SIMREP_CONFIG:-c3} --sim-world $P --multi replicated --steps 3 --no-cpu-baseline --no-ingest $SIMOPTS > $OUT/bench_simrep${P}_${SIMREP_CONFIG:-c3}.json 2> $OUT/bench_simrep$P.err
+      timeout -k 10 600 python -u bench.py --full --config ${SIMREP_CONFIG:-c3} --sim-world $P --multi replicated --steps 3 --no-cpu-baseline --no-ingest $SIMOPTS > $OUT/bench_simrep${P}_${SIMREP_CONFIG:-c3}.json 2> $OUT/bench_simrep$P.err
       rc=$?; echo "bench sim replicated $P rc=$rc"; python3 -c "import json;d=json.load(open('$OUT/bench_simrep${P}_${SIMREP_CONFIG:-c3}.json'));print(round(d['ms_per_step'],3), d['value'], d['undirected_edges'], d['parity'].get('digest_ok'), [round(x,3) for x in d.get('sim_rank_ms')], {k:round(v,3) for k,v in d['device_ms'].items()})"; [ $rc -ne 0 ] && break
     done ;;
   simbkt)
     for P in ${SIMP:-2 4 8}; do
-      timeout -k 10 600 python -u bench.py --config ${SIMREP_CONFIG:-c3} --sim-world $P --multi bucket --steps 3 --no-cpu-baseline --no-ingest $SIMOPTS > $OUT/bench_simbkt${P}_${SIMREP_CONFIG:-c3}.json 2> $OUT/bench_simbkt$P.err
+      timeout -k 10 600 python -u bench.py --full --config ${SIMREP_CONFIG:-c3} --sim-world $P --multi bucket --steps 3 --no-cpu-baseline --no-ingest $SIMOPTS > $OUT/bench_simbkt${P}_${SIMREP_CONFIG:-c3}.json 2> $OUT/bench_simbkt$P.err
       rc=$?; echo "bench sim bucket $P rc=$rc"; python3 -c "import json;d=json.load(open('$OUT/bench_simbkt${P}_${SIMREP_CONFIG:-c3}.json'));print(round(d['ms_per_step'],3), d['value'], d['undirected_edges'], d['parity'].get('digest_ok'), [round(x,3) for x in d.get('sim_rank_ms')], {k:round(v,3) for k,v in d['device_ms'].items()})"; [ $rc -ne 0 ] && break
     done ;;
   xchg1)
-    timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --exchange --steps 5 --no-cpu-baseline --no-ingest > $OUT/bench_xchg1.json 2> $OUT/bench_xchg1.err
+    timeout -k 10 300 python -u -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --exchange --steps 5 --no-cpu-baseline --no-ingest > $OUT/bench_xchg1.json 2> $OUT/bench_xchg1.err
     rc=$?; echo "bench exchange(RCCL, 1 rank) rc=$rc"; python3 -c "import json;d=json.load(open('$OUT/bench_xchg1.json'));print('ms/step',round(d['ms_per_step'],3),'edges',d['undirected_edges'],'digest_ok',d['parity'].get('digest_ok'),'reruns',d.get('exchange_reruns'),{k:round(v,3) for k,v in d['device_ms'].items()},d.get('phase_wall_ms'))" ;;
   profxchg1)
     export MASTER_ADDR=127.0.0.1 MASTER_PORT=29513 RANK=0 WORLD_SIZE=1 LOCAL_RANK=0
@@ -78,7 +78,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for V in "" "$MG_AB"; do
           o=""; for kv in $V; do o="$o --opt $kv"; done
-          MG_SIM_SERIAL=1 timeout -k 10 400 python -u bench.py --config $C --sim-world 8 --multi exchange --steps 3 --no-cpu-baseline --no-ingest --opt layout_scratch=0 $o > $OUT/simab.json 2> $OUT/simab.err
+          MG_SIM_SERIAL=1 timeout -k 10 400 python -u bench.py --full --config $C --sim-world 8 --multi exchange --steps 3 --no-cpu-baseline --no-ingest --opt layout_scratch=0 $o > $OUT/simab.json 2> $OUT/simab.err
           rc=$?; [ $rc -ne 0 ] && break 3
           python3 -c "import json;d=json.load(open('$OUT/simab.json'));print('$C','[$V]','ms/step',round(d['ms_per_step'],3),'digest_ok',d['parity'].get('digest_ok'),{k:round(v,2) for k,v in (d.get('phase_wall_ms') or {}).items()})" | tee -a $OUT/simab.log
         done
@@ -91,7 +91,7 @@ for s in $STEPS; do
       for rep in 1 2; do
         for V in "" "$MG_AB"; do
           o=""; for kv in $V; do o="$o --opt $kv"; done
-          timeout -k 10 400 python -u bench.py --config $C --steps 5 --no-cpu-baseline --no-ingest --no-one-shot --no-d2h $o > $OUT/fusedab.json 2> $OUT/fusedab.err
+          timeout -k 10 400 python -u bench.py --full --config $C --steps 5 --no-cpu-baseline --no-ingest --no-one-shot --no-d2h $o > $OUT/fusedab.json 2> $OUT/fusedab.err
           rc=$?; [ $rc -ne 0 ] && break 3
           python3 -c "import json;d=json.load(open('$OUT/fusedab.json'));print('$C','[$V]','ms/step',round(d['ms_per_step'],3),'digest_ok',d['parity'].get('digest_ok'),{k:round(v,3) for k,v in d['device_ms'].items() if v})" | tee -a $OUT/fusedab.log
         done
@@ -102,7 +102,7 @@ for s in $STEPS; do
     IFS=';' read -ra sets <<< "${OPTSETS}"
     for V in "" "${sets[@]}"; do
       o=""; for kv in $V; do o="$o --opt $kv"; done
-      timeout -k 10 400 python -u bench.py --config ${SWEEP_CONFIG:-c5} --steps 3 --no-cpu-baseline --no-ingest --no-one-shot --no-d2h $o > $OUT/optsweep.json 2> $OUT/optsweep.err
+      timeout -k 10 400 python -u bench.py --full --config ${SWEEP_CONFIG:-c5} --steps 3 --no-cpu-baseline --no-ingest --no-one-shot --no-d2h $o > $OUT/optsweep.json 2> $OUT/optsweep.err
       rc=$?; [ $rc -ne 0 ] && break
       python3 -c "import json;d=json.load(open('$OUT/optsweep.json'));print('${SWEEP_CONFIG:-c5}','[$V]','ms/step',round(d['ms_per_step'],3),'digest_ok',d['parity'].get('digest_ok'),{k:round(v,3) for k,v in d['device_ms'].items() if v},{k:v for k,v in d['counters'].items() if v})" | tee -a $OUT/optsweep.log
     done ;;
@@ -112,7 +112,7 @@ for s in $STEPS; do
     for rep in 1 2; do
       for L in default $LIBS; do
         if [ "$L" = default ]; then lib=""; else lib=$PWD/metagenomics_amd/lib/variants/$L.so; fi
-        MG_LIB=$lib timeout -k 10 400 python -u bench.py --config ${LIBAB_CONFIG:-c5} --steps 5 --no-cpu-baseline --no-ingest --no-one-shot --no-d2h > $OUT/libab.json 2> $OUT/libab.err
+        MG_LIB=$lib timeout -k 10 400 python -u bench.py --full --config ${LIBAB_CONFIG:-c5} --steps 5 --no-cpu-baseline --no-ingest --no-one-shot --no-d2h > $OUT/libab.json 2> $OUT/libab.err
         rc=$?; [ $rc -ne 0 ] && break 2
         python3 -c "import json;d=json.load(open('$OUT/libab.json'));print('${LIBAB_CONFIG:-c5}','$L','ms/step',round(d['ms_per_step'],3),'digest_ok',d['parity'].get('digest_ok'),{k:round(v,3) for k,v in d['device_ms'].items() if v})" | tee -a $OUT/libab.log
       done
@@ -121,10 +121,10 @@ for s in $STEPS; do
     timeout -k 10 300 python -u tools/a2a_probe.py > $OUT/a2a_probe.log 2>&1
     rc=$?; echo "a2a_probe rc=$rc"; grep MB $OUT/a2a_probe.log ;;
   benchq)
-    timeout -k 10 300 python -u bench.py --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err
+    timeout -k 10 300 python -u bench.py --full --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err
     rc=$?; echo "benchq rc=$rc"; python3 -c "import json;d=json.load(open('$OUT/benchq.json'));print('ms/step',round(d['ms_per_step'],3),'edges',d['undirected_edges'],{k:round(v,3) for k,v in d['device_ms'].items()})" ;;
   replay)
-    timeout -k 10 600 python -u bench.py --replay --no-cpu-baseline --no-ingest --steps 2 > $OUT/bench_replay.json 2> $OUT/bench_replay.err
+    timeout -k 10 600 python -u bench.py --full --replay --no-cpu-baseline --no-ingest --steps 2 > $OUT/bench_replay.json 2> $OUT/bench_replay.err
     rc=$?; echo "bench replay rc=$rc"; python3 -c "import json;d=json.load(open('$OUT/bench_replay.json'));print(d.get('graph_replay'))" ;;
   parse)
     timeout -k 10 900 python -u tools/parse_bench.py > $OUT/parse_bench.json 2> $OUT/parse_bench.err
@@ -139,13 +139,13 @@ for s in $STEPS; do
     timeout -k 10 400 python -u tools/phase_sweep.py > $OUT/phase_sweep.log 2>&1
     rc=$?; echo "phases rc=$rc"; grep phase $OUT/phase_sweep.log ;;
   benchc2)
-    timeout -k 10 300 python -u bench.py --config c2 --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench_c2.err
+    timeout -k 10 300 python -u bench.py --full --config c2 --no-cpu-baseline > $OUT/bench_c2.json 2> $OUT/bench_c2.err
     rc=$?; echo "bench c2 rc=$rc"; cat $OUT/bench_c2.json ;;
   benchc5)
-    timeout -k 10 600 python -u bench.py --config c5 --no-ingest > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+    timeout -k 10 600 python -u bench.py --full --config c5 --no-ingest > $OUT/bench_c5.json 2> $OUT/bench_c5.err
     rc=$?; echo "bench c5 rc=$rc"; cat $OUT/bench_c5.json ;;
   benchc5s)
-    timeout -k 10 300 python -u bench.py --config c5s --no-cpu-baseline --no-ingest > $OUT/bench_c5s.json 2> $OUT/bench_c5s.err
+    timeout -k 10 300 python -u bench.py --full --config c5s --no-cpu-baseline --no-ingest > $OUT/bench_c5s.json 2> $OUT/bench_c5s.err
     rc=$?; echo "bench c5s rc=$rc"; cat $OUT/bench_c5s.json ;;
   prof)
     timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o kt -- python3 bench.py --steps 5 --no-cpu-baseline --no-ingest --no-one-shot > $OUT/prof_bench.json 2> $OUT/prof_bench.err

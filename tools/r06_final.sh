@@ -20,13 +20,13 @@ case "$1" in
     run tests && ! grep -qE "[0-9]+ (failed|error)" $OUT/gpu_tests.log &&
     run smoke &&
     run pmc && test -f $OUT/pmc_summary.json &&
-    timeout -k 10 600 python -u bench.py --pmc $OUT/pmc_summary.json > $OUT/bench.json 2> $OUT/bench.err &&
+    timeout -k 10 600 python -u bench.py --full --pmc $OUT/pmc_summary.json > $OUT/bench.json 2> $OUT/bench.err &&
     echo "bench ok" && head -c 600 $OUT/bench.json && echo &&
     run prof &&
     run xchg1 ;;
   B)
     run pmc5 && test -f $OUT/pmc5_summary.json &&
-    timeout -k 10 600 python -u bench.py --config c5 --no-ingest --pmc $OUT/pmc5_summary.json > $OUT/bench_c5.json 2> $OUT/bench_c5.err &&
+    timeout -k 10 600 python -u bench.py --full --config c5 --no-ingest --pmc $OUT/pmc5_summary.json > $OUT/bench_c5.json 2> $OUT/bench_c5.err &&
     echo "bench c5 ok" && head -c 600 $OUT/bench_c5.json && echo &&
     SIMC=c5 SIMP=8 run profsimP ;;
   C)
