@@ -72,6 +72,14 @@ typedef struct mg_counters {
   /* run records the last window scan wrote (every source read's windows; kept
    * without option "stats") */
   uint64_t scan_runs;
+  /* host-side values of the last step (mg_build_index / mg_xchg_begin .. the
+   * discovery probe), kept without option "stats".  A step starts at the build:
+   * a second mg_find_overlaps over the same index starts row_reruns again but
+   * keeps the build's run_reruns (containment may have rescanned before it);
+   * probe_vsplit is that of its own probe launch */
+  uint64_t row_reruns;   /* reruns of the discovery probe after a row-capacity overflow */
+  uint64_t run_reruns;   /* rescans after a run-region overflow */
+  uint64_t probe_vsplit; /* virtual region split of the last discovery probe launch (1 = none) */
 } mg_counters;
 
 /* --- context ------------------------------------------------------------ */
@@ -314,7 +322,8 @@ int mg_get_timings(const mg_ctx* ctx, mg_timings* t);
 int mg_get_counters(const mg_ctx* ctx, mg_counters* c);
 /* Options (results never depend on any of them):
  *  "nb_log2"        log2 directory buckets (0 = auto);
- *  "rows_cap"       initial row capacity (0 = auto);
+ *  "rows_cap"       initial row capacity (0 = auto; overflowing regions are resized
+ *                   and the probe reruns);
  *  "stats"          1 = count work units (mg_get_counters) in the next launches;
  *  "layout"         1 = slots clustered by canonical global minimizer (default),
  *                   0 = ID order; takes effect at the next upload;

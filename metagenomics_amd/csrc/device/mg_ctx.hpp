@@ -129,6 +129,10 @@ struct mg_ctx {
   bool stats = false;
   unsigned long long* d_stats = nullptr;
   mg_counters counters{};
+  // host-side counters of the current step (mg_counters, kept without option "stats"):
+  // discovery reruns after a row overflow (settle_rows), rescans after a run-region
+  // overflow (settle_runs), the virtual split of the last discovery probe launch
+  uint64_t row_reruns = 0, run_reruns = 0, probe_vsplit = 1;
   // shard
   uint32_t rank = 0, nranks = 1;
   uint64_t read_lo = 0, read_hi = 0;  // source-read range: reference IDs - 1 = slots [read_lo, read_hi)

@@ -3560,6 +3560,7 @@ struct LaunchScan {
 
 int settle_rows(mg_ctx* ctx, bool* again);
 int settle_runs(mg_ctx* ctx, bool* again);
+int zero_stats(mg_ctx* ctx);
 
 // k_probe over run regions (runs + r * run_cap, run_cnt[r] records), rows into
 // ctx->d_rows (one region per probe wavefront) or superkey updates (contain).
@@ -3665,6 +3666,7 @@ struct LaunchProbe {
     const bool dcnt = !contain && ctx->xchg && ctx->xchg_route_rows && ctx->nranks > 1 &&
                       ctx->nranks <= (uint32_t)kWave && ctx->n;
     if (!contain) ctx->rows_counted = false;
+    if (!contain) ctx->probe_vsplit = pp.vsplit;
     if (dcnt) {  // the rows' routing takes these counts (mg_xchg_pack, MG_ROWS)
       MG_ENSURE(d_dcnt, dcnt_cap, ctx->nreg * ctx->nranks);
       pp.dst_cnt = ctx->d_dcnt;
@@ -3847,6 +3849,8 @@ int long_probe(mg_ctx* ctx, bool contain, uint64_t a_lo, uint64_t a_hi) {
     return hipGetLastError() == hipSuccess ? 0 : launch_fail(ctx, "long-read containment launch failed");
   }
   ctx->nreg = (uint64_t)grid * kWavesPerBlock;
+  // (the long-read kernels count no work units: option "stats" reads zeros here)
+  if (zero_stats(ctx)) return -1;
   for (int attempt = 0; attempt < 3; ++attempt) {
     p.rows = ctx->d_rows;
     p.reg_cnt = ctx->d_seg;
@@ -3897,6 +3901,7 @@ int settle_runs(mg_ctx* ctx, bool* again) {
   ctx->scan_runs = total;
   if (run_max > ctx->run_cap) {
     ctx->run_cap_need = run_max + run_max / 8 + 64;
+    ++ctx->run_reruns;
     *again = true;
   }
   return 0;
@@ -3908,6 +3913,7 @@ int settle_rows(mg_ctx* ctx, bool* again);
 // the exact need is known, so resize and rerun.
 int run_discover(mg_ctx* ctx, bool contain) {
   for (int attempt = 0; attempt < 3; ++attempt) {
+    if (!contain && zero_stats(ctx)) return -1;
     const int rc = dispatch_w<LaunchDiscover>(ctx->maxw, ctx, contain);
     if (rc < 0) return launch_fail(ctx, "discovery launch failed");  // (keeps the callee's cause)
     bool again = false;
@@ -4451,10 +4457,17 @@ int ensure_rows(mg_ctx* ctx, uint64_t nsrc) {
     if (ctx_malloc(ctx, (void**)&ctx->d_rows, want * 3 * sizeof(uint32_t), "d_rows (row regions)")) return -1;
     ctx->rows_cap = want;
   }
-  if (ctx->stats) {
-    if (!ctx->d_stats) MG_TRY(hipMalloc(&ctx->d_stats, (kSegs * 4 + 1) * sizeof(unsigned long long)));
-    MG_TRY(hipMemsetAsync(ctx->d_stats, 0, (kSegs * 4 + 1) * sizeof(unsigned long long), ctx->stream));
-  }
+  return 0;
+}
+
+// The discovery work counters (option "stats") start from zero with every
+// probe attempt that starts from scratch: a rerun after a row or run overflow
+// repeats the whole probe, so its counts replace the cut attempt's.  (The
+// appended second part of a split exchange probe continues the first.)
+int zero_stats(mg_ctx* ctx) {
+  if (!ctx->stats) return 0;
+  if (!ctx->d_stats) MG_TRY(hipMalloc(&ctx->d_stats, (kSegs * 4 + 1) * sizeof(unsigned long long)));
+  MG_TRY(hipMemsetAsync(ctx->d_stats, 0, (kSegs * 4 + 1) * sizeof(unsigned long long), ctx->stream));
   return 0;
 }
 
@@ -4480,6 +4493,7 @@ int settle_rows(mg_ctx* ctx, bool* again) {
     ctx->rows_cap = 0;
     if (ctx_malloc(ctx, (void**)&ctx->d_rows, want * 3 * sizeof(uint32_t), "d_rows (row regions)")) return -1;
     ctx->rows_cap = want;
+    ++ctx->row_reruns;
     *again = true;
     return 0;
   }
@@ -4826,6 +4840,7 @@ int probe_shared(mg_ctx* ctx, bool contain) {
     }
     if (!contain && attempt == 0 && ctx->contained_done && build_live_index(ctx)) return -1;
     if (live_runs_join(ctx, side)) return -1;
+    if (!contain && zero_stats(ctx)) return -1;
     if (dispatch_w<LaunchProbeShared>(ctx->maxw, ctx, contain)) return launch_fail(ctx, "probe launch failed");
     MG_TRY(hipEventRecord(ctx->ev[9], ctx->stream));
     if (contain) return 0;
@@ -5097,6 +5112,8 @@ int mg_build_index(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k) {
   MG_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
   if (setup_cells(ctx)) return -1;
   ctx->scan_state = 0;
+  ctx->row_reruns = ctx->run_reruns = 0;  // (a new step)
+  ctx->probe_vsplit = 1;
   ctx->t.sort_ms = 0.f;
   ctx->shared_scan_ms = 0.f;
   const bool mixed = ctx->minlen != ctx->maxlen;
@@ -5223,6 +5240,7 @@ int mg_find_overlaps(mg_ctx* ctx, uint64_t* n_rows) {
   if (!ctx->contained_done && mg_mark_contained(ctx, nullptr)) return -1;
   const uint64_t nsrc = (ctx->read_hi ? std::min(ctx->read_hi, ctx->n) : ctx->n) -
                         std::min(ctx->read_lo, ctx->n);
+  ctx->row_reruns = 0;
   if (ensure_rows(ctx, nsrc)) return -1;
   MG_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
   if (long_mode(ctx)) {
@@ -5302,6 +5320,8 @@ int mg_xchg_begin(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k) {
   // this rank's cells: mg_xchg_insert_keys writes every one of them (no clear)
   MG_ENSURE(d_cells, cells_cap, ctx->cell_n * kCell);
   ctx->xchg = true;
+  ctx->row_reruns = ctx->run_reruns = 0;  // (a new step)
+  ctx->probe_vsplit = 1;
   ctx->xruns_ready = false;
   ctx->own_probed = false;
   ctx->xruns_part = 0;
@@ -5644,6 +5664,7 @@ int mg_xchg_probe(mg_ctx* ctx, int contain, const void* recv, uint64_t slot, uin
     if (attempt == 0 && ctx->contained_done && (ctx->super_any || !ctx->index_o3) && build_live_index_xchg(ctx))
       return -1;
     if (live_runs_join(ctx, side)) return -1;
+    if (!(split && attempt == 0) && zero_stats(ctx)) return -1;  // (split: the own part's counts continue)
     if (nregions && dispatch_w<LaunchProbeSlots>(ctx->maxw, ctx, false, runs, reg, nregions, split && attempt == 0))
       return launch_fail(ctx, "probe launch failed");
     MG_TRY(hipEventRecord(ctx->ev[5], ctx->stream));
@@ -5691,6 +5712,7 @@ int mg_xchg_probe_own(mg_ctx* ctx, const void* recv, uint64_t slot, uint32_t rou
   ctx->n_rows = 0;
   MG_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
   if (prepare_xruns(ctx, recv, slot, rounds, reinterpret_cast<const unsigned long long*>(send_counts), 1)) return -1;
+  if (zero_stats(ctx)) return -1;
   if (ctx->xruns_nreg &&
       dispatch_w<LaunchProbeSlots>(ctx->maxw, ctx, false, ctx->xruns_base, ctx->xruns_reg, ctx->xruns_nreg, false))
     return launch_fail(ctx, "probe launch failed");
@@ -5953,6 +5975,9 @@ int mg_get_counters(const mg_ctx* ctx, mg_counters* c) {
   if (!ctx || !c) return -1;
   *c = ctx->counters;
   c->scan_runs = ctx->scan_runs;
+  c->row_reruns = ctx->row_reruns;
+  c->run_reruns = ctx->run_reruns;
+  c->probe_vsplit = ctx->probe_vsplit;
   return 0;
 }
 

@@ -343,6 +343,9 @@ def test_two_processes_default_mode(name, mode):
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([x for x in out.stdout.splitlines() if x.startswith("{")][-1])
     assert r["n_gpus"] == 2 and mode in r["config"]["parallelism"]
+    # (both parallelism strings name bucket-range shards: the mode --multi auto picked is in multi_mode)
+    assert r["multi_mode"]["requested"] == "auto"
+    assert r["multi_mode"]["mode"] == {"c2": "bucket", "c5s": "exchange"}[name], r["multi_mode"]
     assert r["parity"]["golden"] and r["parity"]["digest_ok"] is True, r["parity"]
 
 
