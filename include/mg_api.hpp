@@ -233,6 +233,11 @@ class OverlapGraph {
   // true (default, as the reference): then run the contraction loop
   // (OverlapGraph.cpp:211-215); false: stop just before it
   static bool contractPaths;
+  // D(A) of every read grouped on the device (mg_build_discoveries; default)
+  // or, off, on the host from the downloaded rows (mg_copy_rows +
+  // Discoveries::build).  Same lists either way.  Until this is called the
+  // environment variable MG_DEVICE_DISC decides (0 = host grouping).
+  static void setDeviceDiscoveries(bool on);
   // the contraction loop's steps (:669-696, :931-988) on the current graph
   // (available once the graph was built with replayExploration)
   UINT64 contractCompositePaths();

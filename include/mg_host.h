@@ -95,6 +95,23 @@ typedef struct mgh_graph mgh_graph;
 /* 0 = ok; -1 bad arguments; -2 rows inconsistent with lens / h; -3 unpaired self rows */
 int mgh_graph_replay(const mg_edge* rows, uint64_t n_rows, const uint16_t* lens, uint64_t n_reads, uint32_t h,
                      mgh_graph** out);
+/* The same replay on the device-grouped lists (mg_build_discoveries +
+ * mg_copy_discoveries, include/mg_overlap.h): start has n_reads + 2 entries.
+ * The handle is mgh_graph_replay's.  0 = ok; -1 bad arguments, start not
+ * monotone, start[n_reads + 1] != n_disc or a dst out of range; -2 a record
+ * inconsistent with lens / h; -3 a list not strictly increasing in (j, dst, o). */
+int mgh_graph_replay_disc(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, const uint16_t* lens,
+                          uint64_t n_reads, uint32_t h, mgh_graph** out);
+/* The host grouping on its own (mg::Discoveries::build, what mgh_graph_replay
+ * starts with): rows -> the lists in the layout mg_copy_discoveries gives
+ * (start: n_reads + 2 entries; disc: cap records, cap >= n_rows is always
+ * enough; either may be NULL).  Same return codes as mgh_graph_replay. */
+int mgh_discoveries_build(const mg_edge* rows, uint64_t n_rows, const uint16_t* lens, uint64_t n_reads, uint32_t h,
+                          uint64_t* start, mg_disc* disc, uint64_t cap, uint64_t* n_disc);
+/* The validation and j pass of mgh_graph_replay_disc on its own
+ * (mg::Discoveries::from_lists), same return codes; builds no graph. */
+int mgh_discoveries_check(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, const uint16_t* lens,
+                          uint64_t n_reads, uint32_t h);
 /* OverlapGraph::readGraphFromFile (OverlapGraph.cpp:1270-1367): a .unitig
  * checkpoint back into a graph (both edges of every record, twins rebuilt,
  * read locations updated); lens[id - 1] of the Dataset it was written for.

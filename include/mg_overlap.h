@@ -165,6 +165,36 @@ int mg_copy_rows(mg_ctx* ctx, mg_edge* out, uint64_t cap, uint64_t* n_copied);
  * (the count mg_copy_rows copies and mg_rows_digest(rows = NULL) digests). */
 uint64_t mg_num_rows(const mg_ctx* ctx);
 
+/* --- per-read discovery lists D(A) ------------------------------------------
+ * One discovery of read A as insertAllEdgesOfRead meets it (OverlapGraph.cpp:
+ * 529-565): partner dst, the Edge's overlapOffset and overlapOrientation, and
+ * the HashTable key o (orient 3 -> 0, 0 -> 1, 2 -> 2, 1 -> 3; :550-556).  The
+ * window is j = offset for o = 0, 2 and j = len(A) - (l - 1) - offset for
+ * o = 1, 3.  8 bytes. */
+typedef struct mg_disc {
+  uint32_t dst;
+  uint16_t offset;
+  uint8_t orient;
+  uint8_t o;
+} mg_disc;
+/* After mg_find_overlaps: group the context's rows into D(A) on the device:
+ * the rows with src = A in insertAllEdgesOfRead's loop order (window j, then
+ * partner ID, then key o, ascending; a total order), a self row (dst = A,
+ * twice in the multiset) once.  *n_disc = total list length; *device_ms
+ * (optional) = HIP-event time of the grouping on the context's stream.
+ * Errors (< 0, message in mg_last_error): no completed mg_find_overlaps for
+ * the current index; a context whose rows are not the whole multiset (nranks
+ * > 1 or a source range set by mg_set_shard, or an exchange-mode build:
+ * multi-rank D(A) is out of scope); and the codes of the host grouping:
+ * -1 a src / dst outside 1..n_reads, -2 a window j outside [1, len - h), -3 a
+ * self row without exactly one identical copy. */
+int mg_build_discoveries(mg_ctx* ctx, uint64_t* n_disc, float* device_ms);
+/* start: n_reads + 2 entries, D(A) = disc[start[A] .. start[A+1]), start[0] =
+ * start[1] = 0; disc: cap records.  Either may be NULL.  Fails unless
+ * mg_build_discoveries ran for the current rows: a later mg_build_index,
+ * upload, ingest, mg_set_shard or mg_find_overlaps invalidates the lists. */
+int mg_copy_discoveries(mg_ctx* ctx, uint64_t* start, mg_disc* disc, uint64_t cap, uint64_t* n_copied);
+
 /* --- sharding (multi-GPU, one process per GPU) ---------------------------- */
 /* Restrict this context to index buckets owned by `rank` of `nranks`
  * (bucket-range sharding) and/or to the source reads with
@@ -376,6 +406,9 @@ int mg_get_counters(const mg_ctx* ctx, mg_counters* c);
  *                   the buffer's name, its size and the HIP error in mg_last_error;
  *  "run_cap"        tests: initial run records per scan region (0 = sized from
  *                   the reads; overflowing regions are resized and rescanned);
+ *  "disc_block_cap" tests: records per read the workgroup sort of mg_build_discoveries
+ *                   takes (0 = default 2,048; at least 64, where the wavefront path
+ *                   ends); longer lists take the segmented radix sort;
  *  "phase_limit", "max_blocks"
  *                   diagnostics: stop the probe after a phase / cap its grid. */
 int mg_set_option(mg_ctx* ctx, const char* name, int64_t value);

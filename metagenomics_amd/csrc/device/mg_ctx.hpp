@@ -1,6 +1,7 @@
 // mg_ctx.hpp — INTERNAL: the device context behind include/mg_overlap.h,
 // shared by the kernel translation units (mg_kernels.hip: index + discovery +
-// exchange; mg_dataset.hip: Dataset ingest on the device).
+// exchange; mg_dataset.hip: Dataset ingest on the device; mg_disc.hip: the
+// per-read discovery lists D(A)).
 #ifndef MG_CTX_HPP_
 #define MG_CTX_HPP_
 #include <hip/hip_runtime.h>
@@ -313,6 +314,38 @@ struct mg_ctx {
   // option "alloc_cap" (tests): a device allocation above this many bytes fails
   // as out of memory (0 = no cap), so the error path is exercised on purpose
   uint64_t alloc_cap = 0;
+  // per-read discovery lists D(A) (mg_disc.hip, mg_build_discoveries): the rows
+  // of the last mg_find_overlaps grouped by src into a CSR array and each
+  // segment sorted by (window j, dst, key o).  rows_found: mg_find_overlaps
+  // completed for the current index; disc_ready: the lists belong to those rows
+  bool rows_found = false;
+  bool disc_ready = false;
+  uint64_t n_disc = 0;
+  uint32_t disc_block_cap = 0;  // option "disc_block_cap" (tests): records the workgroup sort takes (0 = 2,048)
+  uint32_t* d_disc_cnt = nullptr;  // rows per src, then the scatter's cursors (n + 2)
+  size_t disc_cnt_cap = 0;
+  uint64_t* d_disc_start = nullptr;  // start[A] (n + 2)
+  size_t disc_start_cap = 0;
+  uint64_t* d_disc = nullptr;  // one 8-B record per row: the sort key, then the mg_disc record
+  size_t disc_cap = 0;
+  uint32_t* d_disc_list = nullptr;  // reads of degree > 64: workgroup path from the front, oversized from the back
+  size_t disc_list_cap = 0;
+  uint32_t* d_disc_boff = nullptr;  // oversized segments: their offsets in d_disc_big
+  size_t disc_boff_cap = 0;
+  uint64_t* d_disc_big[2] = {nullptr, nullptr};  // oversized segments gathered for the segmented radix sort
+  size_t disc_big_cap[2] = {0, 0};
+  uint8_t* d_disc_tmp = nullptr;  // rocprim temporary storage (scans, segmented sort)
+  size_t disc_tmp_cap = 0;
+  unsigned long long* d_disc_ctl = nullptr;  // kDiscCtl control words (errors, class counts, self duplicates)
+  size_t disc_ctl_cap = 0;
+  // self rows only (tandem repeats): the duplicate-free copy and its starts
+  uint64_t* d_disc_alt = nullptr;
+  size_t disc_alt_cap = 0;
+  uint64_t* d_disc_start_alt = nullptr;
+  size_t disc_start_alt_cap = 0;
+  uint32_t* d_disc_pre = nullptr;  // kept records before each record
+  size_t disc_pre_cap = 0;
+  hipEvent_t disc_ev[2] = {};
 };
 
 #define MG_TRY(expr)                                                                  \
@@ -408,6 +441,11 @@ inline void reset_derived(mg_ctx* ctx) {
   ctx->live_coarse = false;
   ctx->n_contained = 0;
   ctx->n_rows = 0;
+  ctx->rows_found = false;
+  ctx->disc_ready = false;
 }
+
+// mg_disc.hip: frees the discovery-list buffers (mg_destroy)
+void disc_release(mg_ctx* ctx);
 
 #endif  // MG_CTX_HPP_

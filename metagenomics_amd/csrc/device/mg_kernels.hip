@@ -3978,6 +3978,7 @@ void mg_destroy(mg_ctx* ctx) {
                   ctx->d_kblk, ctx->d_rdst, ctx->d_cells_alt};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
+  disc_release(ctx);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -4198,6 +4199,10 @@ int mg_set_option(mg_ctx* ctx, const char* name, int64_t value) {
     ctx->alloc_cap = (uint64_t)std::max<int64_t>(0, value);
     return 0;
   }
+  if (!strcmp(name, "disc_block_cap")) {  // tests: records the discovery lists' workgroup sort takes (0 = default)
+    ctx->disc_block_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+    return 0;
+  }
   if (!strcmp(name, "run_cap")) {  // tests: initial run records per scan region (0 = sized from the reads)
     ctx->run_cap_opt = (uint64_t)std::max<int64_t>(0, value);
     ctx->run_cap_need = 0;
@@ -4279,6 +4284,8 @@ int setup_index(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k, bool cells =
   ctx->contained_done = false;
   ctx->super_any = false;
   ctx->live_ready = false;
+  ctx->rows_found = false;  // (the rows and the discovery lists belong to the last index)
+  ctx->disc_ready = false;
   ctx->key0_ready = false;  // set by the fused build when it writes the o = 0 keys
   ctx->xchg = false;        // mg_xchg_begin sets it after this
   ctx->xchg_fused = false;  // (a plain build after a one-rank exchange step takes no exchange shortcut)
@@ -5241,6 +5248,8 @@ int mg_find_overlaps(mg_ctx* ctx, uint64_t* n_rows) {
   const uint64_t nsrc = (ctx->read_hi ? std::min(ctx->read_hi, ctx->n) : ctx->n) -
                         std::min(ctx->read_lo, ctx->n);
   ctx->row_reruns = 0;
+  ctx->rows_found = false;
+  ctx->disc_ready = false;
   if (ensure_rows(ctx, nsrc)) return -1;
   MG_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
   if (long_mode(ctx)) {
@@ -5256,6 +5265,7 @@ int mg_find_overlaps(mg_ctx* ctx, uint64_t* n_rows) {
     ctx->t.overlap_ms = ctx->t.probe_ms;
     ctx->t.total_ms = ctx->t.index_ms + ctx->t.contained_ms + ctx->t.overlap_ms;
     read_stats(ctx, nsrc);
+    ctx->rows_found = true;
     if (n_rows) *n_rows = ctx->n_rows;
     return 0;
   }
@@ -5275,6 +5285,7 @@ int mg_find_overlaps(mg_ctx* ctx, uint64_t* n_rows) {
   // device wall of the step: index build start .. last discovery kernel end
   ctx->t.total_ms = shared_scan(ctx) ? elapsed(ctx->ev[0], ctx->ev[5])
                                      : ctx->t.index_ms + ctx->t.contained_ms + ctx->t.overlap_ms;
+  ctx->rows_found = true;
   if (n_rows) *n_rows = ctx->n_rows;
   return 0;
 }

@@ -24,6 +24,8 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <thread>
+#include <utility>
 #include <vector>
 
 #include "mg_graph.hpp"
@@ -243,7 +245,80 @@ int Discoveries::build(const mg_edge* rows, uint64_t n_rows, const uint16_t* len
   return 0;
 }
 
+int Discoveries::from_lists(const uint64_t* start_in, const mg_disc* d, uint64_t n_disc, const uint16_t* lens,
+                            uint64_t n_reads, uint32_t h) {
+  if (start_in[0] != 0 || start_in[1] != 0) return -1;
+  for (uint64_t a = 1; a <= n_reads; ++a)
+    if (start_in[a + 1] < start_in[a]) return -1;
+  if (start_in[n_reads + 1] != n_disc) return -1;
+  start.assign(start_in, start_in + n_reads + 2);
+  disc.assign(n_disc, Disc{});
+  // one pass over the records of reads [lo, hi): Disc with j recomputed, each
+  // list strictly increasing in (j, dst, o); the first bad read and its code
+  auto pass = [&](uint64_t lo, uint64_t hi, uint64_t* bad_read, int* bad_rc) {
+    for (uint64_t a = lo; a < hi; ++a) {
+      const int64_t n1 = lens[a - 1];
+      int rc = 0;
+      for (uint64_t k = start[a]; k < start[a + 1] && !rc; ++k) {
+        const mg_disc& r = d[k];
+        if (r.dst < 1 || r.dst > n_reads) {
+          rc = -1;
+          break;
+        }
+        if (r.orient > 3 || r.o != orient_to_key(r.orient)) {
+          rc = -2;
+          break;
+        }
+        const int64_t j = (r.o == 0 || r.o == 2) ? r.offset : n1 - (int64_t)h - r.offset;
+        if (j < 1 || j >= n1 - (int64_t)h) {
+          rc = -2;
+          break;
+        }
+        disc[k] = Disc{(uint32_t)j, r.dst, r.o, r.orient, r.offset};
+        if (k > start[a]) {  // the loop order is total
+          const Disc& p = disc[k - 1];
+          const Disc& c = disc[k];
+          const bool less = p.j != c.j ? p.j < c.j : p.r2 != c.r2 ? p.r2 < c.r2 : p.o < c.o;
+          if (!less) rc = -3;
+        }
+      }
+      if (rc) {
+        *bad_read = a;
+        *bad_rc = rc;
+        return;
+      }
+    }
+  };
+  // the reads are independent: threads take ranges of about equal record counts
+  const unsigned hw = std::thread::hardware_concurrency();
+  const uint64_t T = n_disc < (1u << 20) ? 1 : std::max<uint64_t>(1, std::min<uint64_t>(16, hw ? hw : 1));
+  std::vector<uint64_t> cut(T + 1, 1), bad_read(T, 0);
+  std::vector<int> bad_rc(T, 0);
+  cut[T] = n_reads + 1;
+  for (uint64_t t = 1; t < T; ++t)  // first read whose list starts at or after record t * n_disc / T
+    cut[t] = std::max<uint64_t>(
+        cut[t - 1], (uint64_t)(std::lower_bound(start.begin() + 1, start.begin() + n_reads + 1, t * (n_disc / T)) -
+                               start.begin()));
+  if (T == 1) {
+    pass(1, n_reads + 1, &bad_read[0], &bad_rc[0]);
+  } else {
+    std::vector<std::thread> th;
+    for (uint64_t t = 0; t < T; ++t) th.emplace_back(pass, cut[t], cut[t + 1], &bad_read[t], &bad_rc[t]);
+    for (auto& x : th) x.join();
+  }
+  for (uint64_t t = 0; t < T; ++t)  // (ranges ascend: the first bad read overall)
+    if (bad_rc[t]) return bad_rc[t];
+  return 0;
+}
+
 int GraphReplay::build(const mg_edge* rows, uint64_t n_rows, const uint16_t* lens, uint64_t n_reads, uint32_t h) {
+  Discoveries D;
+  const int rc = D.build(rows, n_rows, lens, n_reads, h);
+  if (rc) return rc;
+  return build_from(std::move(D), lens, n_reads, h);
+}
+
+int GraphReplay::build_from(Discoveries&& D, const uint16_t* lens, uint64_t n_reads, uint32_t h) {
   Impl& I = *impl;
   I.len = lens;
   I.n = n_reads;
@@ -251,12 +326,9 @@ int GraphReplay::build(const mg_edge* rows, uint64_t n_rows, const uint16_t* len
   pool.clear();
   lists.assign(n_reads + 1, {});
   nodes = edges = 0;
-  Discoveries D;
-  const int rc = D.build(rows, n_rows, lens, n_reads, h);
-  if (rc) return rc;
   I.dstart.swap(D.start);
   I.disc.swap(D.disc);
-  pool.reserve(n_rows);
+  pool.reserve(I.disc.size());
   I.run();
   return 0;
 }

@@ -39,6 +39,14 @@ struct Discoveries {
   // rows: the full directed multiset (any order); lens[id - 1]; h = l - 1.
   // 0 = ok, < 0 = rows inconsistent with the lengths / h.
   int build(const mg_edge* rows, uint64_t n_rows, const uint16_t* lens, uint64_t n_reads, uint32_t h);
+  // The same lists from the device's grouping (mg_build_discoveries +
+  // mg_copy_discoveries): start_in has n_reads + 2 entries.  One linear pass
+  // fills Disc (j recomputed) and validates what it is given: 0 = ok, -1 start
+  // not monotone from 0 / start[n_reads + 1] != n_disc / a dst outside
+  // 1..n_reads, -2 a window j outside [1, len - h) or a key o that does not
+  // belong to the orientation, -3 a list not strictly increasing in (j, dst, o).
+  int from_lists(const uint64_t* start_in, const mg_disc* d, uint64_t n_disc, const uint16_t* lens, uint64_t n_reads,
+                 uint32_t h);
 };
 
 class GraphReplay {
@@ -50,6 +58,8 @@ class GraphReplay {
   // rows: the full directed discovery multiset (any order); lens[id - 1]; h = l - 1.
   // 0 = ok, < 0 = rows inconsistent with the lengths / h.
   int build(const mg_edge* rows, uint64_t n_rows, const uint16_t* lens, uint64_t n_reads, uint32_t h);
+  // the same replay on lists already grouped (Discoveries::build / from_lists); always 0
+  int build_from(Discoveries&& D, const uint16_t* lens, uint64_t n_reads, uint32_t h);
   std::vector<GraphEdge> pool;               // every Edge ever created (removed ones stay, unlisted)
   std::vector<std::vector<uint32_t>> lists;  // graph[u]: pool indices in list order
   uint64_t nodes = 0, edges = 0;             // numberOfNodes, numberOfEdges

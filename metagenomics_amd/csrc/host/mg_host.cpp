@@ -701,6 +701,40 @@ bool OverlapGraph::insertEdge(Read* read1, Read* read2, UINT8 orient, UINT16 ove
   return true;
 }
 
+namespace {
+// D(A) of every read of the (unsharded) context: grouped on the device
+// (mg_build_discoveries, the default) or on the host from the downloaded rows.
+// g_device_disc: OverlapGraph::setDeviceDiscoveries; -1 = not called, the
+// environment variable MG_DEVICE_DISC decides (unset: device)
+int g_device_disc = -1;
+
+bool env_device_disc() {
+  const char* v = std::getenv("MG_DEVICE_DISC");
+  return v && *v ? std::atoi(v) != 0 : true;
+}
+
+void discoveries_of(mg_ctx* ctx, uint64_t nrows, const uint16_t* lens, UINT64 N, uint32_t h, mg::Discoveries* D) {
+  const bool device = g_device_disc < 0 ? env_device_disc() : g_device_disc != 0;
+  if (device) {
+    uint64_t nd = 0, got = 0;
+    if (mg_build_discoveries(ctx, &nd, nullptr)) mg::fail(ctx, "build discoveries");
+    std::vector<uint64_t> start(N + 2, 0);
+    std::vector<mg_disc> recs(nd);
+    if (mg_copy_discoveries(ctx, start.data(), recs.data(), nd, &got) || got != nd) mg::fail(ctx, "copy discoveries");
+    const int rc = D->from_lists(start.data(), recs.data(), nd, lens, N, h);
+    if (rc) throw mg::Error("discoveries inconsistent with the Dataset (" + std::to_string(rc) + ")");
+    return;
+  }
+  std::vector<mg_edge> rows(nrows);
+  uint64_t got = 0;
+  if (mg_copy_rows(ctx, rows.data(), nrows, &got)) mg::fail(ctx, "copy rows");
+  const int rc = D->build(rows.data(), got, lens, N, h);
+  if (rc) throw mg::Error("discoveries inconsistent with the Dataset (" + std::to_string(rc) + ")");
+}
+}  // namespace
+
+void OverlapGraph::setDeviceDiscoveries(bool on) { g_device_disc = on ? 1 : 0; }
+
 bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
   // OverlapGraph.cpp:107-218 up to the end of edge discovery: containment,
   // then every insertEdge of the exploration, on the device
@@ -716,13 +750,13 @@ bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
   mg_ctx* ctx = ht->context();
   uint64_t nrows = 0;
   if (mg_find_overlaps(ctx, &nrows)) mg::fail(ctx, "buildOverlapGraphFromHashTable");
-  std::vector<mg_edge> rows(nrows);
-  uint64_t got = 0;
-  if (mg_copy_rows(ctx, rows.data(), nrows, &got)) mg::fail(ctx, "copy rows");
   mg_get_timings(ctx, &lastTimings);
   if (!replayExploration) {
     // the raw discovery multiset: rows come in (edge, twin) pairs, as
     // insertEdge(Read*,...) creates them
+    std::vector<mg_edge> rows(nrows);
+    uint64_t got = 0;
+    if (mg_copy_rows(ctx, rows.data(), nrows, &got)) mg::fail(ctx, "copy rows");
     for (uint64_t k = 0; k + 1 < got; k += 2) {
       Read* u = dataSet->getReadFromID(rows[k].src);
       Read* v = dataSet->getReadFromID(rows[k].dst);
@@ -740,10 +774,11 @@ bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
     }
   } else {
     // the reference's exploration order + transitive reduction (:144-204,
-    // 574-661) replayed on the rows: same lists, same order, same counters
+    // 574-661) replayed on the discoveries: same lists, same order, same counters
     mg::GraphReplay rp;
-    const int rc = rp.build(rows.data(), got, dataSet->packedLengths(), N, (uint32_t)ht->getHashStringLength());
-    if (rc) throw mg::Error("graph replay: rows inconsistent with the Dataset (" + std::to_string(rc) + ")");
+    mg::Discoveries D;
+    discoveries_of(ctx, nrows, dataSet->packedLengths(), N, (uint32_t)ht->getHashStringLength(), &D);
+    rp.build_from(std::move(D), dataSet->packedLengths(), N, (uint32_t)ht->getHashStringLength());
     unitig = new mg::UnitigGraph();
     unitig->init(rp, N, true);
     if (contractPaths && unitig->contract() < 0) throw mg::Error("Unable to merge.");  // :211-215
@@ -770,14 +805,10 @@ bool OverlapGraph::beginBuildFromHashTable(HashTable* ht) {
   mg_ctx* ctx = ht->context();
   uint64_t nrows = 0;
   if (mg_find_overlaps(ctx, &nrows)) mg::fail(ctx, "beginBuildFromHashTable");
-  std::vector<mg_edge> rows(nrows);
-  uint64_t got = 0;
-  if (mg_copy_rows(ctx, rows.data(), nrows, &got)) mg::fail(ctx, "copy rows");
   mg_get_timings(ctx, &lastTimings);
   manual = new Manual();
   manual->h = ht->getHashStringLength();
-  const int rc = manual->D.build(rows.data(), got, dataSet->packedLengths(), N, (uint32_t)manual->h);
-  if (rc) throw mg::Error("discoveries inconsistent with the Dataset (" + std::to_string(rc) + ")");
+  discoveries_of(ctx, nrows, dataSet->packedLengths(), N, (uint32_t)manual->h, &manual->D);
   // the table stays the caller's, who frees it after the build as the reference
   // does (:210, mg_explore_main.cpp): nothing here reads it again (h is captured)
   hashTable = nullptr;
@@ -1061,6 +1092,53 @@ int mgh_graph_replay(const mg_edge* rows, uint64_t n_rows, const uint16_t* lens,
     return -1;
   }
   return 0;
+}
+
+int mgh_graph_replay_disc(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, const uint16_t* lens,
+                          uint64_t n_reads, uint32_t h, mgh_graph** out) {
+  if (!out || !start || (n_disc && !disc) || (n_reads && !lens)) return -1;
+  *out = nullptr;
+  try {
+    mg::Discoveries D;
+    const int rc = D.from_lists(start, disc, n_disc, lens, n_reads, h);
+    if (rc) return rc;
+    std::unique_ptr<mgh_graph> g(new mgh_graph());
+    g->g.build_from(std::move(D), lens, n_reads, h);
+    *out = g.release();
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_discoveries_build(const mg_edge* rows, uint64_t n_rows, const uint16_t* lens, uint64_t n_reads, uint32_t h,
+                          uint64_t* start, mg_disc* disc, uint64_t cap, uint64_t* n_disc) {
+  if ((n_rows && !rows) || (n_reads && !lens)) return -1;
+  if (n_disc) *n_disc = 0;
+  try {
+    mg::Discoveries D;
+    const int rc = D.build(rows, n_rows, lens, n_reads, h);
+    if (rc) return rc;
+    if (start) std::copy(D.start.begin(), D.start.end(), start);
+    if (disc)
+      for (uint64_t k = 0; k < D.disc.size() && k < cap; ++k)
+        disc[k] = mg_disc{D.disc[k].r2, D.disc[k].offset, D.disc[k].orient, D.disc[k].o};
+    if (n_disc) *n_disc = D.disc.size();
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_discoveries_check(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, const uint16_t* lens,
+                          uint64_t n_reads, uint32_t h) {
+  if (!start || (n_disc && !disc) || (n_reads && !lens)) return -1;
+  try {
+    mg::Discoveries D;
+    return D.from_lists(start, disc, n_disc, lens, n_reads, h);
+  } catch (const std::exception&) {
+    return -1;
+  }
 }
 
 int mgh_graph_read_unitig(const char* path, const uint16_t* lens, uint64_t n_reads, mgh_graph** out) {

@@ -22,6 +22,8 @@ LIB_PATH = os.environ.get("MG_LIB") or os.path.join(_HERE, "lib", "libmgovl.so")
 MG_KEYS, MG_RUNS, MG_ROWS = 0, 1, 2
 
 EDGE_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("flags", "u1")])
+# one discovery of a read's list D(A) (mg_disc, include/mg_overlap.h): 8 bytes
+DISC_DTYPE = np.dtype([("dst", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("o", "u1")])
 
 
 class MgError(RuntimeError):
@@ -80,6 +82,8 @@ def lib() -> C.CDLL:
         "mg_mark_contained": (i32, [vp, vp]),
         "mg_find_overlaps": (i32, [vp, P(u64)]),
         "mg_copy_rows": (i32, [vp, vp, u64, P(u64)]),
+        "mg_build_discoveries": (i32, [vp, P(u64), P(C.c_float)]),
+        "mg_copy_discoveries": (i32, [vp, vp, vp, u64, P(u64)]),
         "mg_set_shard": (i32, [vp, u32, u32, u64, u64]),
         "mg_get_timings": (i32, [vp, P(_Timings)]),
         "mg_get_counters": (i32, [vp, P(_Counters)]),
@@ -115,6 +119,9 @@ def lib() -> C.CDLL:
         "mgh_frequency": (u32, [vp, u64]),
         "mgh_find_read": (u64, [vp, C.c_char_p, u64]),
         "mgh_graph_replay": (i32, [vp, u64, vp, u64, u32, P(vp)]),
+        "mgh_graph_replay_disc": (i32, [vp, vp, u64, vp, u64, u32, P(vp)]),
+        "mgh_discoveries_build": (i32, [vp, u64, vp, u64, u32, vp, vp, u64, P(u64)]),
+        "mgh_discoveries_check": (i32, [vp, vp, u64, vp, u64, u32]),
         "mgh_graph_free": (None, [vp]),
         "mgh_graph_nodes": (u64, [vp]),
         "mgh_graph_edges": (u64, [vp]),
@@ -420,6 +427,26 @@ class OverlapEngine:
         self._check(lib().mg_copy_rows(self._h, C.c_void_p(host_ptr), cap, C.byref(got)), "copy_rows")
         return int(got.value)
 
+    # --- per-read discovery lists D(A), grouped and ordered on the device
+    def build_discoveries(self) -> int:
+        """mg_build_discoveries: the rows of the last find_overlaps grouped into
+        every read's D(A) in insertAllEdgesOfRead's loop order.  Returns the total
+        list length; disc_ms keeps the device time of the grouping."""
+        n, ms = C.c_uint64(), C.c_float()
+        self._check(lib().mg_build_discoveries(self._h, C.byref(n), C.byref(ms)), "build_discoveries")
+        self.disc_ms = float(ms.value)
+        self._n_disc = int(n.value)
+        return self._n_disc
+
+    def discoveries(self):
+        """(start uint64[n_reads + 2], disc[DISC_DTYPE]): D(A) = disc[start[A]:start[A + 1]]."""
+        n = getattr(self, "_n_disc", 0)
+        start = np.zeros(self.n_reads + 2, dtype=np.uint64)
+        disc = np.zeros(n, dtype=DISC_DTYPE)
+        got = C.c_uint64()
+        self._check(lib().mg_copy_discoveries(self._h, _ptr(start), _ptr(disc), n, C.byref(got)), "copy_discoveries")
+        return start, disc[: got.value]
+
     def lookup(self, key: str):
         n = C.c_uint64()
         cap = 1024
@@ -542,6 +569,60 @@ def replay_graph(rows: np.ndarray, lens: np.ndarray, min_overlap: int):
         L.mgh_graph_free(g)
 
 
+def _replay_disc(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int) -> C.c_void_p:
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    disc = np.ascontiguousarray(disc, dtype=DISC_DTYPE)
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    if start.shape[0] != lens.shape[0] + 2:
+        raise MgError("discovery lists: start must have n_reads + 2 entries")
+    g = C.c_void_p()
+    rc = lib().mgh_graph_replay_disc(_ptr(start), _ptr(disc), disc.shape[0], _ptr(lens), lens.shape[0],
+                                     min_overlap - 1, C.byref(g))
+    if rc:
+        raise MgError(f"graph replay failed ({rc})")
+    return g
+
+
+def host_discoveries(rows: np.ndarray, lens: np.ndarray, min_overlap: int):
+    """The host grouping of rows into per-read lists (mgh_discoveries_build,
+    mg::Discoveries::build): (start, disc) as OverlapEngine.discoveries gives them."""
+    rows = np.ascontiguousarray(rows, dtype=EDGE_DTYPE)
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    start = np.zeros(lens.shape[0] + 2, dtype=np.uint64)
+    disc = np.zeros(rows.shape[0], dtype=DISC_DTYPE)
+    n = C.c_uint64()
+    rc = lib().mgh_discoveries_build(_ptr(rows), rows.shape[0], _ptr(lens), lens.shape[0], min_overlap - 1,
+                                     _ptr(start), _ptr(disc), disc.shape[0], C.byref(n))
+    if rc:
+        raise MgError(f"host grouping failed ({rc})")
+    return start, disc[: n.value]
+
+
+def check_discoveries(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int) -> int:
+    """mgh_discoveries_check: 0 when the lists are well formed (mg::Discoveries::from_lists), else its code."""
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    disc = np.ascontiguousarray(disc, dtype=DISC_DTYPE)
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    if start.shape[0] != lens.shape[0] + 2:
+        raise MgError("discovery lists: start must have n_reads + 2 entries")
+    return int(lib().mgh_discoveries_check(_ptr(start), _ptr(disc), disc.shape[0], _ptr(lens), lens.shape[0],
+                                           min_overlap - 1))
+
+
+def replay_discoveries(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int):
+    """replay_graph on the per-read discovery lists (OverlapEngine.discoveries,
+    mgh_graph_replay_disc): the same (numberOfNodes, numberOfEdges, list rows)."""
+    L = lib()
+    g = _replay_disc(start, disc, lens, min_overlap)
+    try:
+        n = int(L.mgh_graph_rows(g, None, 0))
+        out = np.zeros(n, dtype=EDGE_DTYPE)
+        L.mgh_graph_rows(g, _ptr(out), n)
+        return int(L.mgh_graph_nodes(g)), int(L.mgh_graph_edges(g)), out
+    finally:
+        L.mgh_graph_free(g)
+
+
 def _parse_result(L, rc, t, o, n, what):
     if rc:
         raise MgError({-1: f"Unable to open file: {what}", -2: f"Unknown input file format: {what}"}.get(
@@ -606,6 +687,22 @@ class UnitigGraph:
                                 C.byref(self._g))
         if rc:
             raise MgError(f"graph replay failed ({rc})")
+        self._contract(t0, track_locations)
+
+    @classmethod
+    def from_discoveries(cls, start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int,
+                         track_locations: bool = True) -> "UnitigGraph":
+        """The same graph from the per-read discovery lists (OverlapEngine.discoveries)."""
+        self = cls.__new__(cls)
+        self._L = lib()
+        self._g = C.c_void_p()
+        t0 = time.perf_counter()
+        self._g = _replay_disc(start, disc, lens, min_overlap)
+        self._contract(t0, track_locations)
+        return self
+
+    def _contract(self, t0: float, track_locations: bool):
+        L = self._L
         self.replay_nodes, self.replay_edges = int(L.mgh_graph_nodes(self._g)), int(L.mgh_graph_edges(self._g))
         t1 = time.perf_counter()
         it, merged, dead = C.c_uint64(), C.c_uint64(), C.c_uint64()
