@@ -238,6 +238,13 @@ class OverlapGraph {
   // Discoveries::build).  Same lists either way.  Until this is called the
   // environment variable MG_DEVICE_DISC decides (0 = host grouping).
   static void setDeviceDiscoveries(bool on);
+  // Connected components of the lists (mg_build_components on the device
+  // lists, a host union-find with host grouping; default on): they are
+  // replayed in parallel by min(16, hardware threads) host threads
+  // (MG_REPLAY_THREADS) unless one component holds 90 % of the records.  Off:
+  // always the serial replay.  The same graph either way.  Until this is
+  // called the environment variable MG_DEVICE_COMP decides (0 = serial).
+  static void setDeviceComponents(bool on);
   // the contraction loop's steps (:669-696, :931-988) on the current graph
   // (available once the graph was built with replayExploration)
   UINT64 contractCompositePaths();

@@ -112,6 +112,23 @@ int mgh_discoveries_build(const mg_edge* rows, uint64_t n_rows, const uint16_t* 
  * (mg::Discoveries::from_lists), same return codes; builds no graph. */
 int mgh_discoveries_check(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, const uint16_t* lens,
                           uint64_t n_reads, uint32_t h);
+/* The connected components of the lists on the host (mg::Components::build, a
+ * plain union-find): what mg_build_components + mg_copy_components give
+ * (include/mg_overlap.h).  label: n_reads + 1 entries; comps: cap entries
+ * (n_reads / 2 is always enough); either may be NULL.  0 = ok, -1 = bad
+ * arguments, start malformed or a dst out of range. */
+int mgh_components_build(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, uint64_t n_reads,
+                         uint32_t* label, mg_comp* comps, uint64_t cap, uint64_t* n_comp);
+/* mgh_graph_replay_disc with the components replayed in parallel by `threads`
+ * host threads (0 = min(16, hardware threads) or MG_REPLAY_THREADS; 1 = the
+ * serial replay): the same handle, the same graph.  label (n_reads + 1
+ * entries) and comps are validated against the lists.  Codes of
+ * mgh_graph_replay_disc, -1 also for a label or root outside 1..n_reads, and
+ * -4 = label / comps are not the components of these lists (no graph is
+ * built). */
+int mgh_graph_replay_comp(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, const uint16_t* lens,
+                          uint64_t n_reads, uint32_t h, const uint32_t* label, const mg_comp* comps, uint64_t n_comp,
+                          uint32_t threads, mgh_graph** out);
 /* OverlapGraph::readGraphFromFile (OverlapGraph.cpp:1270-1367): a .unitig
  * checkpoint back into a graph (both edges of every record, twins rebuilt,
  * read locations updated); lens[id - 1] of the Dataset it was written for.

@@ -195,6 +195,32 @@ int mg_build_discoveries(mg_ctx* ctx, uint64_t* n_disc, float* device_ms);
  * upload, ingest, mg_set_shard or mg_find_overlaps invalidates the lists. */
 int mg_copy_discoveries(mg_ctx* ctx, uint64_t* start, mg_disc* disc, uint64_t cap, uint64_t* n_copied);
 
+/* --- connected components of the discovery lists ----------------------------
+ * Two reads are connected when a discovery record joins them.  The reference's
+ * outer loop (OverlapGraph.cpp:144-204) explores one component at a time from
+ * its smallest read ID, so components can be replayed independently
+ * (mgh_graph_replay_comp, include/mg_host.h).  One component that holds at
+ * least one record: */
+typedef struct mg_comp { /* 16 bytes */
+  uint32_t root;         /* smallest read ID of the component */
+  uint32_t n_reads;      /* reads in it */
+  uint32_t n_disc;       /* records of their lists D(A), self records once */
+  uint32_t n_self;       /* of those, records with dst == A */
+} mg_comp;
+/* After mg_build_discoveries: label every read with the smallest read ID
+ * connected to it (itself for a read with an empty list) and list the
+ * components that hold records in strictly ascending root, all on the device
+ * (union-find over the resident lists).  Labels and table are functions of the
+ * lists alone: two calls give identical arrays.  *n_comp = table length;
+ * *device_ms (optional) = HIP-event time on the context's stream.  Errors (< 0)
+ * as mg_build_discoveries refuses (sharded / source range / exchange mode), and
+ * unless mg_build_discoveries ran for the current rows. */
+int mg_build_components(mg_ctx* ctx, uint64_t* n_comp, float* device_ms);
+/* label: n_reads + 1 entries, label[0] = 0; comps: cap entries.  Either may be
+ * NULL.  Fails unless mg_build_components ran for the current lists: whatever
+ * invalidates the lists, and every mg_build_discoveries, invalidates it. */
+int mg_copy_components(mg_ctx* ctx, uint32_t* label, mg_comp* comps, uint64_t cap, uint64_t* n_copied);
+
 /* --- sharding (multi-GPU, one process per GPU) ---------------------------- */
 /* Restrict this context to index buckets owned by `rank` of `nranks`
  * (bucket-range sharding) and/or to the source reads with

@@ -346,6 +346,20 @@ struct mg_ctx {
   uint32_t* d_disc_pre = nullptr;  // kept records before each record
   size_t disc_pre_cap = 0;
   hipEvent_t disc_ev[2] = {};
+  // connected components of the discovery lists (mg_comp.hip, mg_build_components):
+  // comp_ready: labels and table belong to the current lists (cleared with
+  // disc_ready and by every mg_build_discoveries)
+  bool comp_ready = false;
+  uint64_t n_comp = 0;
+  uint32_t* d_comp_parent = nullptr;  // union-find parent[0 .. n + 1]; after the flatten: reads per root
+  size_t comp_parent_cap = 0;
+  uint32_t* d_comp_label = nullptr;  // label[0 .. n + 1], label[0] = 0
+  size_t comp_label_cap = 0;
+  uint32_t* d_comp_acc = nullptr;  // per root: records [0, n + 2), self records [n + 2, 2 (n + 2))
+  size_t comp_acc_cap = 0;
+  mg_comp* d_comp = nullptr;  // the table, ascending root
+  size_t comp_cap = 0;
+  hipEvent_t comp_ev[2] = {};
 };
 
 #define MG_TRY(expr)                                                                  \
@@ -443,9 +457,23 @@ inline void reset_derived(mg_ctx* ctx) {
   ctx->n_rows = 0;
   ctx->rows_found = false;
   ctx->disc_ready = false;
+  ctx->comp_ready = false;
 }
 
 // mg_disc.hip: frees the discovery-list buffers (mg_destroy)
 void disc_release(mg_ctx* ctx);
+// mg_comp.hip: frees the component buffers (mg_destroy)
+void comp_release(mg_ctx* ctx);
+
+// D(A) and what is derived from it need the whole multiset in one context
+inline int whole_multiset(mg_ctx* ctx, const char* who) {
+  if (ctx->nranks > 1 || ctx->read_lo || ctx->read_hi)
+    return set_err(ctx, std::string(who) + ": the context is sharded (mg_set_shard): its rows are not the whole "
+                                           "multiset; multi-rank D(A) is not supported");
+  if (ctx->xchg || ctx->xchg_fused)
+    return set_err(ctx, std::string(who) + ": exchange-mode build: its rows are not the whole multiset; multi-rank "
+                                           "D(A) is not supported");
+  return 0;
+}
 
 #endif  // MG_CTX_HPP_

@@ -333,16 +333,6 @@ int read_ctl(mg_ctx* ctx, unsigned long long* host) {
   return 0;
 }
 
-int whole_multiset(mg_ctx* ctx, const char* who) {
-  if (ctx->nranks > 1 || ctx->read_lo || ctx->read_hi)
-    return set_err(ctx, std::string(who) + ": the context is sharded (mg_set_shard): its rows are not the whole "
-                                           "multiset; multi-rank D(A) is not supported");
-  if (ctx->xchg || ctx->xchg_fused)
-    return set_err(ctx, std::string(who) + ": exchange-mode build: its rows are not the whole multiset; multi-rank "
-                                           "D(A) is not supported");
-  return 0;
-}
-
 int group_rows(mg_ctx* ctx) {
   const uint64_t N = ctx->n, R = ctx->n_rows, entries = N + 2;
   const uint32_t h = ctx->h;
@@ -477,6 +467,7 @@ int mg_build_discoveries(mg_ctx* ctx, uint64_t* n_disc, float* device_ms) {
   if (n_disc) *n_disc = 0;
   if (device_ms) *device_ms = 0.f;
   ctx->disc_ready = false;
+  ctx->comp_ready = false;
   if (whole_multiset(ctx, "mg_build_discoveries")) return -1;
   if (!ctx->index_ready || !ctx->rows_found)
     return set_err(ctx, "mg_build_discoveries: mg_find_overlaps must complete for the current index first");

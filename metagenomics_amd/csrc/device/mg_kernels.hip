@@ -3979,6 +3979,7 @@ void mg_destroy(mg_ctx* ctx) {
   for (void* b : bufs)
     if (b) (void)hipFree(b);
   disc_release(ctx);
+  comp_release(ctx);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -4286,6 +4287,7 @@ int setup_index(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k, bool cells =
   ctx->live_ready = false;
   ctx->rows_found = false;  // (the rows and the discovery lists belong to the last index)
   ctx->disc_ready = false;
+  ctx->comp_ready = false;
   ctx->key0_ready = false;  // set by the fused build when it writes the o = 0 keys
   ctx->xchg = false;        // mg_xchg_begin sets it after this
   ctx->xchg_fused = false;  // (a plain build after a one-rank exchange step takes no exchange shortcut)
@@ -5250,6 +5252,7 @@ int mg_find_overlaps(mg_ctx* ctx, uint64_t* n_rows) {
   ctx->row_reruns = 0;
   ctx->rows_found = false;
   ctx->disc_ready = false;
+  ctx->comp_ready = false;
   if (ensure_rows(ctx, nsrc)) return -1;
   MG_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
   if (long_mode(ctx)) {

@@ -713,8 +713,35 @@ bool env_device_disc() {
   return v && *v ? std::atoi(v) != 0 : true;
 }
 
-void discoveries_of(mg_ctx* ctx, uint64_t nrows, const uint16_t* lens, UINT64 N, uint32_t h, mg::Discoveries* D) {
+// The component table for the parallel replay (mg_build_components on the
+// device lists, mg::Components::build with host grouping).  g_device_comp:
+// OverlapGraph::setDeviceComponents; -1 = not called, the environment variable
+// MG_DEVICE_COMP decides (unset: on; 0 = the serial replay)
+int g_device_comp = -1;
+
+bool env_device_comp() {
+  const char* v = std::getenv("MG_DEVICE_COMP");
+  return v && *v ? std::atoi(v) != 0 : true;
+}
+
+// A component that holds this share of the records bounds the parallel
+// replay's gain at 1 / share: from here on the table is not worth its
+// validation and the pool's up-front sizing, and the replay
+// stays serial.
+constexpr double kSerialShare = 0.9;
+
+bool worth_parallel(const std::vector<mg_comp>& comps, uint64_t n_disc) {
+  uint64_t top = 0;
+  for (const mg_comp& c : comps) top = std::max<uint64_t>(top, c.n_disc);
+  return comps.size() > 1 && (double)top < kSerialShare * (double)n_disc;
+}
+
+// D(A) of every read; with C != nullptr also the components, when the parallel
+// replay is switched on and worth it: returns whether *C was filled.
+bool discoveries_of(mg_ctx* ctx, uint64_t nrows, const uint16_t* lens, UINT64 N, uint32_t h, mg::Discoveries* D,
+                    mg::Components* C = nullptr) {
   const bool device = g_device_disc < 0 ? env_device_disc() : g_device_disc != 0;
+  const bool comp = C && (g_device_comp < 0 ? env_device_comp() : g_device_comp != 0) && mg::replay_threads() > 1;
   if (device) {
     uint64_t nd = 0, got = 0;
     if (mg_build_discoveries(ctx, &nd, nullptr)) mg::fail(ctx, "build discoveries");
@@ -723,17 +750,31 @@ void discoveries_of(mg_ctx* ctx, uint64_t nrows, const uint16_t* lens, UINT64 N,
     if (mg_copy_discoveries(ctx, start.data(), recs.data(), nd, &got) || got != nd) mg::fail(ctx, "copy discoveries");
     const int rc = D->from_lists(start.data(), recs.data(), nd, lens, N, h);
     if (rc) throw mg::Error("discoveries inconsistent with the Dataset (" + std::to_string(rc) + ")");
-    return;
+    if (!comp) return false;
+    uint64_t nc = 0;
+    if (mg_build_components(ctx, &nc, nullptr)) mg::fail(ctx, "build components");
+    std::vector<mg_comp> table(nc);
+    if (mg_copy_components(ctx, nullptr, table.data(), nc, &got) || got != nc) mg::fail(ctx, "copy components");
+    if (!worth_parallel(table, nd)) return false;  // (before the labels are copied and checked)
+    std::vector<uint32_t> label(N + 1, 0);
+    if (mg_copy_components(ctx, label.data(), nullptr, 0, &got)) mg::fail(ctx, "copy components");
+    const int rc2 = C->from_device(label.data(), table.data(), nc, *D);
+    if (rc2) throw mg::Error("components inconsistent with the discovery lists (" + std::to_string(rc2) + ")");
+    return true;
   }
   std::vector<mg_edge> rows(nrows);
   uint64_t got = 0;
   if (mg_copy_rows(ctx, rows.data(), nrows, &got)) mg::fail(ctx, "copy rows");
   const int rc = D->build(rows.data(), got, lens, N, h);
   if (rc) throw mg::Error("discoveries inconsistent with the Dataset (" + std::to_string(rc) + ")");
+  if (!comp) return false;
+  if (C->build(*D)) throw mg::Error("components: a partner ID out of range");
+  return worth_parallel(C->comps, D->disc.size());
 }
 }  // namespace
 
 void OverlapGraph::setDeviceDiscoveries(bool on) { g_device_disc = on ? 1 : 0; }
+void OverlapGraph::setDeviceComponents(bool on) { g_device_comp = on ? 1 : 0; }
 
 bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
   // OverlapGraph.cpp:107-218 up to the end of edge discovery: containment,
@@ -777,8 +818,12 @@ bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
     // 574-661) replayed on the discoveries: same lists, same order, same counters
     mg::GraphReplay rp;
     mg::Discoveries D;
-    discoveries_of(ctx, nrows, dataSet->packedLengths(), N, (uint32_t)ht->getHashStringLength(), &D);
-    rp.build_from(std::move(D), dataSet->packedLengths(), N, (uint32_t)ht->getHashStringLength());
+    mg::Components C;  // components are independent: replayed in parallel when there are several
+    const bool par =
+        discoveries_of(ctx, nrows, dataSet->packedLengths(), N, (uint32_t)ht->getHashStringLength(), &D, &C);
+    const int rc = rp.build_from(std::move(D), dataSet->packedLengths(), N, (uint32_t)ht->getHashStringLength(),
+                                 par ? &C : nullptr, par ? mg::replay_threads() : 1);
+    if (rc) throw mg::Error("components inconsistent with the discovery lists (" + std::to_string(rc) + ")");
     unitig = new mg::UnitigGraph();
     unitig->init(rp, N, true);
     if (contractPaths && unitig->contract() < 0) throw mg::Error("Unable to merge.");  // :211-215
@@ -1104,6 +1149,60 @@ int mgh_graph_replay_disc(const uint64_t* start, const mg_disc* disc, uint64_t n
     if (rc) return rc;
     std::unique_ptr<mgh_graph> g(new mgh_graph());
     g->g.build_from(std::move(D), lens, n_reads, h);
+    *out = g.release();
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+namespace {
+// the lists as Components::build reads them (start, partner IDs); false = start malformed
+bool partners_of(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, uint64_t n_reads, mg::Discoveries* D) {
+  if (start[0] != 0 || start[1] != 0 || start[n_reads + 1] != n_disc) return false;
+  for (uint64_t a = 1; a <= n_reads; ++a)
+    if (start[a + 1] < start[a]) return false;
+  D->start.assign(start, start + n_reads + 2);
+  D->disc.assign(n_disc, mg::Disc{});
+  for (uint64_t k = 0; k < n_disc; ++k) D->disc[k].r2 = disc[k].dst;
+  return true;
+}
+}  // namespace
+
+int mgh_components_build(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, uint64_t n_reads,
+                         uint32_t* label, mg_comp* comps, uint64_t cap, uint64_t* n_comp) {
+  if (!start || (n_disc && !disc)) return -1;
+  if (n_comp) *n_comp = 0;
+  try {
+    mg::Discoveries D;
+    if (!partners_of(start, disc, n_disc, n_reads, &D)) return -1;
+    mg::Components C;
+    const int rc = C.build(D);
+    if (rc) return rc;
+    if (label) std::copy(C.label.begin(), C.label.end(), label);
+    if (comps) std::copy(C.comps.begin(), C.comps.begin() + std::min<uint64_t>(cap, C.comps.size()), comps);
+    if (n_comp) *n_comp = C.comps.size();
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_graph_replay_comp(const uint64_t* start, const mg_disc* disc, uint64_t n_disc, const uint16_t* lens,
+                          uint64_t n_reads, uint32_t h, const uint32_t* label, const mg_comp* comps, uint64_t n_comp,
+                          uint32_t threads, mgh_graph** out) {
+  if (!out || !start || (n_disc && !disc) || (n_reads && !lens) || !label || (n_comp && !comps)) return -1;
+  *out = nullptr;
+  try {
+    mg::Discoveries D;
+    int rc = D.from_lists(start, disc, n_disc, lens, n_reads, h);
+    if (rc) return rc;
+    mg::Components C;
+    rc = C.from_device(label, comps, n_comp, D);
+    if (rc) return rc;
+    std::unique_ptr<mgh_graph> g(new mgh_graph());
+    rc = g->g.build_from(std::move(D), lens, n_reads, h, &C, threads ? threads : mg::replay_threads());
+    if (rc) return rc;
     *out = g.release();
   } catch (const std::exception&) {
     return -1;

@@ -24,6 +24,8 @@ MG_KEYS, MG_RUNS, MG_ROWS = 0, 1, 2
 EDGE_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("flags", "u1")])
 # one discovery of a read's list D(A) (mg_disc, include/mg_overlap.h): 8 bytes
 DISC_DTYPE = np.dtype([("dst", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("o", "u1")])
+# one connected component of the discovery lists (mg_comp, include/mg_overlap.h): 16 bytes
+COMP_DTYPE = np.dtype([("root", "<u4"), ("n_reads", "<u4"), ("n_disc", "<u4"), ("n_self", "<u4")])
 
 
 class MgError(RuntimeError):
@@ -84,6 +86,8 @@ def lib() -> C.CDLL:
         "mg_copy_rows": (i32, [vp, vp, u64, P(u64)]),
         "mg_build_discoveries": (i32, [vp, P(u64), P(C.c_float)]),
         "mg_copy_discoveries": (i32, [vp, vp, vp, u64, P(u64)]),
+        "mg_build_components": (i32, [vp, P(u64), P(C.c_float)]),
+        "mg_copy_components": (i32, [vp, vp, vp, u64, P(u64)]),
         "mg_set_shard": (i32, [vp, u32, u32, u64, u64]),
         "mg_get_timings": (i32, [vp, P(_Timings)]),
         "mg_get_counters": (i32, [vp, P(_Counters)]),
@@ -122,6 +126,8 @@ def lib() -> C.CDLL:
         "mgh_graph_replay_disc": (i32, [vp, vp, u64, vp, u64, u32, P(vp)]),
         "mgh_discoveries_build": (i32, [vp, u64, vp, u64, u32, vp, vp, u64, P(u64)]),
         "mgh_discoveries_check": (i32, [vp, vp, u64, vp, u64, u32]),
+        "mgh_components_build": (i32, [vp, vp, u64, u64, vp, vp, u64, P(u64)]),
+        "mgh_graph_replay_comp": (i32, [vp, vp, u64, vp, u64, u32, vp, vp, u64, u32, P(vp)]),
         "mgh_graph_free": (None, [vp]),
         "mgh_graph_nodes": (u64, [vp]),
         "mgh_graph_edges": (u64, [vp]),
@@ -447,6 +453,28 @@ class OverlapEngine:
         self._check(lib().mg_copy_discoveries(self._h, _ptr(start), _ptr(disc), n, C.byref(got)), "copy_discoveries")
         return start, disc[: got.value]
 
+    # --- connected components of the lists, labelled on the device
+    def build_components(self) -> int:
+        """mg_build_components: label every read with the smallest read ID its
+        discovery records connect it to and list the components that hold
+        records, on the device.  Returns the number of components; comp_ms keeps
+        the device time."""
+        n, ms = C.c_uint64(), C.c_float()
+        self._n_comp = None
+        self._check(lib().mg_build_components(self._h, C.byref(n), C.byref(ms)), "build_components")
+        self.comp_ms = float(ms.value)
+        self._n_comp = int(n.value)
+        return self._n_comp
+
+    def components(self):
+        """(label uint32[n_reads + 1], comps[COMP_DTYPE] in ascending root): label[0] = 0."""
+        n = getattr(self, "_n_comp", None) or 0
+        label = np.zeros(int(lib().mg_num_reads(self._h)) + 1, dtype=np.uint32)
+        comps = np.zeros(n, dtype=COMP_DTYPE)
+        got = C.c_uint64()
+        self._check(lib().mg_copy_components(self._h, _ptr(label), _ptr(comps), n, C.byref(got)), "copy_components")
+        return label, comps[: got.value]
+
     def lookup(self, key: str):
         n = C.c_uint64()
         cap = 1024
@@ -569,18 +597,46 @@ def replay_graph(rows: np.ndarray, lens: np.ndarray, min_overlap: int):
         L.mgh_graph_free(g)
 
 
-def _replay_disc(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int) -> C.c_void_p:
+def _replay_disc(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int, components=None,
+                 threads: int = 0) -> C.c_void_p:
     start = np.ascontiguousarray(start, dtype=np.uint64)
     disc = np.ascontiguousarray(disc, dtype=DISC_DTYPE)
     lens = np.ascontiguousarray(lens, dtype=np.uint16)
     if start.shape[0] != lens.shape[0] + 2:
         raise MgError("discovery lists: start must have n_reads + 2 entries")
     g = C.c_void_p()
-    rc = lib().mgh_graph_replay_disc(_ptr(start), _ptr(disc), disc.shape[0], _ptr(lens), lens.shape[0],
-                                     min_overlap - 1, C.byref(g))
+    if components is None:
+        rc = lib().mgh_graph_replay_disc(_ptr(start), _ptr(disc), disc.shape[0], _ptr(lens), lens.shape[0],
+                                         min_overlap - 1, C.byref(g))
+    else:
+        label = np.ascontiguousarray(components[0], dtype=np.uint32)
+        comps = np.ascontiguousarray(components[1], dtype=COMP_DTYPE)
+        if label.shape[0] != lens.shape[0] + 1:
+            raise MgError("components: label must have n_reads + 1 entries")
+        rc = lib().mgh_graph_replay_comp(_ptr(start), _ptr(disc), disc.shape[0], _ptr(lens), lens.shape[0],
+                                         min_overlap - 1, _ptr(label), _ptr(comps), comps.shape[0], max(0, threads),
+                                         C.byref(g))
     if rc:
         raise MgError(f"graph replay failed ({rc})")
     return g
+
+
+def host_components(start: np.ndarray, disc: np.ndarray):
+    """The components of the lists from the host union-find (mgh_components_build,
+    mg::Components::build): (label, comps) as OverlapEngine.components gives them."""
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    disc = np.ascontiguousarray(disc, dtype=DISC_DTYPE)
+    if start.shape[0] < 2:
+        raise MgError("discovery lists: start must have n_reads + 2 entries")
+    n_reads = start.shape[0] - 2
+    label = np.zeros(n_reads + 1, dtype=np.uint32)
+    comps = np.zeros(n_reads // 2 + 1, dtype=COMP_DTYPE)
+    n = C.c_uint64()
+    rc = lib().mgh_components_build(_ptr(start), _ptr(disc), disc.shape[0], n_reads, _ptr(label), _ptr(comps),
+                                    comps.shape[0], C.byref(n))
+    if rc:
+        raise MgError(f"host components failed ({rc})")
+    return label, comps[: n.value]
 
 
 def host_discoveries(rows: np.ndarray, lens: np.ndarray, min_overlap: int):
@@ -609,11 +665,16 @@ def check_discoveries(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min
                                            min_overlap - 1))
 
 
-def replay_discoveries(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int):
+def replay_discoveries(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int, components=None,
+                       threads: int = 0):
     """replay_graph on the per-read discovery lists (OverlapEngine.discoveries,
-    mgh_graph_replay_disc): the same (numberOfNodes, numberOfEdges, list rows)."""
+    mgh_graph_replay_disc): the same (numberOfNodes, numberOfEdges, list rows).
+    components = (label, comps) (OverlapEngine.components / host_components):
+    the components are replayed in parallel by `threads` host threads (0 = the
+    default, mgh_graph_replay_comp); the same result, or MgError (-4) for a
+    table that is not the lists'."""
     L = lib()
-    g = _replay_disc(start, disc, lens, min_overlap)
+    g = _replay_disc(start, disc, lens, min_overlap, components, threads)
     try:
         n = int(L.mgh_graph_rows(g, None, 0))
         out = np.zeros(n, dtype=EDGE_DTYPE)
@@ -691,13 +752,14 @@ class UnitigGraph:
 
     @classmethod
     def from_discoveries(cls, start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int,
-                         track_locations: bool = True) -> "UnitigGraph":
-        """The same graph from the per-read discovery lists (OverlapEngine.discoveries)."""
+                         track_locations: bool = True, components=None, threads: int = 0) -> "UnitigGraph":
+        """The same graph from the per-read discovery lists (OverlapEngine.discoveries);
+        components / threads as in replay_discoveries."""
         self = cls.__new__(cls)
         self._L = lib()
         self._g = C.c_void_p()
         t0 = time.perf_counter()
-        self._g = _replay_disc(start, disc, lens, min_overlap)
+        self._g = _replay_disc(start, disc, lens, min_overlap, components, threads)
         self._contract(t0, track_locations)
         return self
 
