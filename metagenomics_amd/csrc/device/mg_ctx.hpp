@@ -19,6 +19,18 @@ __host__ __device__ constexpr int slot_words(int w) {
   return w <= 1 ? 1 : w <= 2 ? 2 : w <= 4 ? 4 : w <= 8 ? 8 : w <= 16 ? 16 : 32;
 }
 
+// The slot's word that carries the read's reference ID - 1 in clustered slots
+// (low 32 bits, high 32 bits 0), or -1 when the width has no
+// spare word: the last word of the slot where it lies beyond word W, the zero
+// pad that load_slot, the scan's rw[MAXW] and ext_slot read.  Written by
+// k_layout_gather, read by k_probe's verification, both at the template width
+// dispatch_w selects (never mg_ctx::maxw: maxw 7 runs template 8, 9-11 run 12).
+__host__ __device__ constexpr int slot_id_word(int w) { return slot_words(w) >= w + 2 ? slot_words(w) - 1 : -1; }
+static_assert(slot_id_word(5) == 7 && slot_id_word(6) == 7 && slot_id_word(12) == 15, "widths with a spare word");
+static_assert(slot_id_word(1) == -1 && slot_id_word(2) == -1 && slot_id_word(3) == -1 && slot_id_word(4) == -1 &&
+                  slot_id_word(8) == -1 && slot_id_word(16) == -1 && slot_id_word(32) == -1,
+              "widths whose slot ends at the pad word (or before it)");
+
 struct mg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;

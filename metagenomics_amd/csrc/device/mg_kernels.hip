@@ -1654,6 +1654,17 @@ __device__ __forceinline__ void load_slot(const uint64_t* words, uint32_t bid, u
   }
 }
 
+// Reference ID - 1 of a clustered slot (id != nullptr): one dword from the
+// slot's own line where the width has a spare word (slot_id_word, written by
+// k_layout_gather), so it costs no request beyond the slot's; else id[slot].
+template <int MAXW>
+__device__ __forceinline__ uint32_t slot_ref_id(const uint64_t* words, const uint32_t* id, uint32_t slot) {
+  if constexpr (slot_id_word(MAXW) >= 0)
+    return *reinterpret_cast<const uint32_t*>(words + (uint64_t)slot * slot_words(MAXW) + slot_id_word(MAXW));
+  else
+    return id[slot];
+}
+
 // Key records of the reverse strand's keys (hashRead, HashTable.cpp:88-104),
 // one thread per read: o = 3 (R[n-h, n) = rc F[0, h): m-mer i = rc of F's at
 // t = w-1-i) and o = 2 (R[0, h) = rc F[n-h, n): m-mer i = rc of F's at
@@ -1918,16 +1929,18 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(MG_PROBE
       // atomicMax(len << 32 | ~id) would be a no-op when the partner already
       // holds a key >= this container's: skip the slot load and the compare
       // (keys only grow, so a stale view only prunes less)
-      const uint32_t ia = p.id ? p.id[sa] : sa;
+      const uint32_t ia = p.id ? slot_ref_id<MAXW>(p.words, p.id, sa) : sa;
       const unsigned long long want = ((unsigned long long)n1 << 32) | (0xFFFFFFFFu - ia);
       cond = __hip_atomic_load(&p.superkey[bid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < want;
     }
     if (cond) {
       load_slot<MAXW>(p.words, bid, y);
-      if (p.id) {
-        ida = p.id[sa];
-        idb = p.id[bid];
+#ifndef MG_DIAG_NO_IDLOAD  // (diagnostics build: rows carry slot numbers -- timing only, the rows are wrong)
+      if (p.id) {  // the partner's ID rides in its slot line, the source's in the line staged below
+        idb = slot_ref_id<MAXW>(p.words, p.id, bid);
+        ida = slot_ref_id<MAXW>(p.words, p.id, sa);
       }
+#endif
     }
     if (have) {  // the source's words, 16 B per load where the slot allows
       const uint64_t* g = p.words + (uint64_t)sa * slot_words(MAXW);
@@ -3037,7 +3050,10 @@ __global__ __launch_bounds__(kBlock) void k_layout_keys(const uint64_t* __restri
 }
 
 // new slot i <- old slot src[i]: its words (16-B pieces), length and reference
-// ID, into the second slot array (committed by swapping)
+// ID, into the second slot array (committed by swapping).  Where
+// the width has a spare word (slot_id_word), every gather also writes the ID
+// there, whatever the source slot held: both slot arrays stay right through
+// any sequence of uploads and re-layouts.
 template <int MAXW>
 __global__ __launch_bounds__(kBlock) void k_layout_gather(const uint64_t* __restrict__ src_words,
                                                          const uint16_t* __restrict__ src_len,
@@ -3053,7 +3069,12 @@ __global__ __launch_bounds__(kBlock) void k_layout_gather(const uint64_t* __rest
   const int k = (int)(t - i * P);
   const uint32_t r = order[i];
   if (S >= 2) {
-    reinterpret_cast<ulonglong2*>(dst_words)[t] = reinterpret_cast<const ulonglong2*>(src_words)[(uint64_t)r * P + k];
+    ulonglong2 x = reinterpret_cast<const ulonglong2*>(src_words)[(uint64_t)r * P + k];
+    if constexpr (slot_id_word(MAXW) >= 0) {  // the slot's last word carries the reference ID (k_probe's verify)
+      static_assert(slot_id_word(MAXW) == 2 * P - 1, "the ID word ends the last 16-B piece");
+      if (k == P - 1) x.y = old_id ? old_id[r] : r;
+    }
+    reinterpret_cast<ulonglong2*>(dst_words)[t] = x;
   } else {
     dst_words[i] = src_words[r];
   }
