@@ -13,6 +13,8 @@
 // Differences, all deliberate:
 //  * errors throw mg::Error instead of MYEXIT's exit(0) (Common.h:47);
 //  * reads are stored 2-bit packed; getStringForward/Reverse decode on demand;
+//  * the mate lists of all reads are one CSR array; Read::getMatePairList()
+//    returns a view with vector's read interface (size, at, [], begin, end);
 //  * OverlapGraph(ht) returns the reference's graph: discovery on the device,
 //    then the reference's exploration order and transitive reduction
 //     and its contraction loop (OverlapGraph.cpp:211-215,
@@ -53,6 +55,34 @@ class Edge;
 enum nodeType { UNEXPLORED = 0, EXPLORED = 1, EXPLORED_AND_TRANSITIVE_EDGES_MARKED = 2 };
 enum markType { VACANT = 0, INPLAY = 1, ELIMINATED = 2 };
 
+// One entry of a read's mate list (Read.h:16-27).
+struct MPlist {
+  UINT64 matePairID;          // ID of the mate
+  UINT8 matePairOrientation;  // 0 = 00 reverse/reverse, 1 = 01 reverse/forward, 2 = 10, 3 = 11 forward/forward
+  UINT8 datasetNumber;        // index of the paired-end file
+};
+
+// Read::getMatePairList()'s result: the read's slice of the Dataset's CSR array,
+// used as the reference uses its vector<MPlist>* (list->size(), list->at(j)).
+class MatePairList {
+ public:
+  MatePairList(const MPlist* b, const MPlist* e) : b_(b), e_(e) {}
+  size_t size() const { return (size_t)(e_ - b_); }
+  bool empty() const { return b_ == e_; }
+  const MPlist& at(size_t i) const {
+    if (i >= size()) throw std::out_of_range("MatePairList::at");
+    return b_[i];
+  }
+  const MPlist& operator[](size_t i) const { return b_[i]; }
+  const MPlist* begin() const { return b_; }
+  const MPlist* end() const { return e_; }
+  const MatePairList* operator->() const { return this; }
+
+ private:
+  const MPlist* b_;
+  const MPlist* e_;
+};
+
 class Read {
  public:
   UINT64 superReadID = 0;      // 0 = not contained, else ID of the super read (Read.h:50)
@@ -62,6 +92,9 @@ class Read {
   UINT16 getReadLength();
   UINT64 getReadNumber() { return readNumber; }
   UINT32 getFrequency();
+  // the mates Dataset::readMatePairsFromFile() stored for this read, in
+  // addMatePair's order (Read.h:65, Read.cpp:132-166); empty before that call
+  MatePairList getMatePairList();
   // composite edges holding this read's forward / reverse string and the read's
   // distance on each (Read.h:39-42, maintained by OverlapGraph.cpp:1048-1115)
   std::vector<Edge*>* getListOfEdgesForward() { return &locations().edgesForward; }
@@ -133,7 +166,12 @@ class Dataset {
   Read* getReadFromString(const std::string& read);
   Read* getReadFromID(UINT64 ID);
   void saveReads(std::string fileName);
-  void readMatePairsFromFile() {}  // single-end only: mate pairs are out of scope
+  // storeMatePairInformation for every paired-end file (Dataset.cpp:97-104,
+  // 208-310): fills every read's mate list.  Nothing to do without paired-end
+  // files.  While an OverlapGraph build holds the device context the lists are
+  // built there (mg_build_mate_pairs; MG_DEVICE_MATES=0: on the host), else by
+  // the host mirror (mg::MatePairs::build).  Same lists either way.
+  void readMatePairsFromFile();
 
   // --- packed view (device upload) and bulk construction (bench / Python) ---
   static Dataset* fromCodes(const uint8_t* codes, uint64_t n, uint64_t stride, const uint16_t* lens,
@@ -146,10 +184,15 @@ class Dataset {
   UINT64 minimumOverlapLength() const { return minOverlapLength; }
 
  private:
+  friend class Read;
+  friend class OverlapGraph;
   Dataset() = default;
   void finalize(mg::PackedReads&& pr);
   mg::PackedReads* packed = nullptr;
   std::vector<Read> reads;
+  mg_ctx* mateCtx = nullptr;        // the device context of a running OverlapGraph build (not owned)
+  std::vector<uint64_t> mateStart;  // n + 2 entries once readMatePairsFromFile ran: the list of read A is
+  std::vector<MPlist> mates;        //   mates[mateStart[A] .. mateStart[A + 1])
   UINT64 numberOfReads = 0, numberOfUniqueReads = 0, minOverlapLength = 0;
 };
 
@@ -216,8 +259,9 @@ class OverlapGraph {
   bool readGraphFromFile(const std::string& fileName);
   UINT64 getNumberOfEdges() { return numberOfEdges; }
   UINT64 getNumberOfNodes() { return numberOfNodes; }
-  bool setDataset(Dataset* d) {
+  bool setDataset(Dataset* d) {  // OverlapGraph.h:79
     dataSet = d;
+    dataSet->readMatePairsFromFile();
     return true;
   }
   // graph[u] of the reference (private there): edges of read u, sorted by offset (:563)

@@ -74,6 +74,36 @@ void mgh_parse_free(void* p);
 /* smallest chunk one thread splits (default 1 MiB; 0 restores it) */
 void mgh_parse_set_min_chunk(uint64_t bytes);
 
+/* --- mate pairs (storeMatePairInformation, Dataset.cpp:208-310) --------------------
+ * The mates of every pair of the paired-end files, file by file, as
+ * storeMatePairInformation's own loop extracts them (not readDataset's):
+ * FASTQ = eight getlines per pair, mates on lines 1 and 5; FASTA = getline,
+ * getline(.., '>'), getline, getline(.., '>') with only '\n' erased; a string
+ * is cleared only while the stream is good.  So a FASTQ file that ends in a
+ * newline gives one more pair of two empty mates, a FASTA file with an odd
+ * record count pairs its last sequence with itself, and CRLF leaves '\r' in.
+ * Records 2p and 2p + 1 are the mates of pair p (bytes as in the file);
+ * pairs_per_file (optional) gets nfiles counts.  Serial.  The outputs are
+ * malloc'ed (mgh_parse_free) and are what mg_find_reads / mg_build_mate_pairs
+ * take.  0 = ok, -1 = cannot open, -2 = unknown format, -3 = bad arguments /
+ * out of memory. */
+int mgh_read_pairs(const char* const* paths, int nfiles, char** text, uint64_t** offsets, uint64_t* n_records,
+                   uint64_t* pairs_per_file, double* seconds);
+int mgh_read_pairs_buffer(const char* buf, uint64_t n, char** text, uint64_t** offsets, uint64_t* n_records);
+/* The host mirror of mg_build_mate_pairs + mg_copy_mate_pairs (mg::MatePairs::
+ * build): the reference's statements (getReadFromString's binary search, the
+ * superReadID redirect, string::find, Read::addMatePair) over the packed unique
+ * reads in ID order; super = superReadID per ID (n_reads + 1 entries) or NULL
+ * (all 0).  start: n_reads + 2 entries; out: cap records (cap >= n_raw is
+ * always enough); either may be NULL.  0 = ok, -1 = bad arguments, -2 = a good
+ * mate has no read (*not_found = its raw index; the reference exits with
+ * "String not found in Dataset"). */
+int mgh_mate_pairs_build(const uint64_t* words, const uint16_t* lens, uint64_t n_reads, uint32_t words_per_read,
+                         const uint32_t* super, const char* concat, const uint64_t* offsets, uint64_t n_raw,
+                         const uint64_t* pairs_per_dataset, uint32_t n_datasets, uint32_t min_overlap,
+                         uint64_t* start, mg_mate* out, uint64_t cap, uint64_t* n_records, uint64_t* good_bad_pairs,
+                         int64_t* not_found);
+
 /* --- multi-process rendezvous (exchange mode over RCCL) ---------
  * Rank 0 serves the n-byte blob (the RCCL unique id) to the world - 1 other
  * ranks over TCP at addr:port; the others receive it into blob.  addr is a

@@ -221,6 +221,55 @@ int mg_build_components(mg_ctx* ctx, uint64_t* n_comp, float* device_ms);
  * invalidates the lists, and every mg_build_discoveries, invalidates it. */
 int mg_copy_components(mg_ctx* ctx, uint32_t* label, mg_comp* comps, uint64_t cap, uint64_t* n_copied);
 
+/* --- read lookup and mate pairs (Dataset::getReadFromString, storeMatePairInformation)
+ * Batched Dataset::getReadFromString (Dataset.cpp:421-455) over the resident
+ * reads.  Raw record i = concat[offsets[i], offsets[i+1]), any case, as
+ * mg_ingest_ascii takes it.  id_out[i] = the reference ID of the resident read
+ * equal to min(s, revcomp s), or 0 when the record fails the ingest's filter
+ * (length > min_overlap, ACGT only, the 80 % rule, length <= 65,535) or no
+ * resident read equals it (the reference exits there; here it is a value).
+ * flags_out[i]: bit 0 = the record passed the filter; bit 1 = a read was found
+ * and the upper-cased record itself is its stored forward string (so a read
+ * that is its own reverse complement sets it).  The search is a binary search
+ * over the reads in ID order = std::string order (packed words, then length).
+ * Works in every context that holds the reads (after any upload or ingest,
+ * layout on or off, sharded and exchange-mode contexts included).
+ * *device_ms (optional) = HIP-event time of the kernels (no transfers). */
+int mg_find_reads(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint64_t n_raw, uint32_t min_overlap,
+                  uint32_t* id_out, uint8_t* flags_out, float* device_ms);
+/* One entry of Read::getMatePairList() (MPlist, Read.h): the mate's read ID,
+ * matePairOrientation 0..3 and datasetNumber.  8 bytes. */
+typedef struct mg_mate {
+  uint32_t id;
+  uint8_t orient;
+  uint8_t dataset;
+  uint16_t pad; /* 0 */
+} mg_mate;
+/* storeMatePairInformation's per-pair body (Dataset.cpp:275-301) and
+ * Read::addMatePair (Read.cpp:132-166) for every pair of every paired-end
+ * file: records 2p and 2p + 1 are line1 and line2 of pair p, pairs in file
+ * order, file by file; pairs_per_dataset[d] pairs belong to file d (their sum
+ * is n_raw / 2; d < 256, UINT8 as in MPlist).  A pair is good iff both mates
+ * pass the filter; r1, r2 = the lookup above; with use_super a read with
+ * superReadID != 0 is replaced by that read (once, :280-284; the IDs of the
+ * context's completed mg_mark_contained); orient_k = 1 iff the upper-cased raw
+ * mate occurs in the forward string of the (redirected) read (:291-292); r1
+ * gets (r2, orient1 * 2 + orient2, d), then r2 gets (r1, orient1 + orient2 * 2,
+ * d), each unless its list already holds an equal entry.  The lists stay on
+ * the device as one CSR until new reads arrive.  *n_records = total list
+ * length; good_bad_pairs[0 / 1] = good / bad pairs.  Errors: n_raw odd or the
+ * dataset counts do not add up; use_super on a sharded, source-range or
+ * exchange-mode context or before mg_mark_contained completed; a good mate
+ * with no resident read (-2; the message names the first such raw index; the
+ * reference exits with "String not found in Dataset"). */
+int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint64_t n_raw,
+                        const uint64_t* pairs_per_dataset, uint32_t n_datasets, uint32_t min_overlap, int use_super,
+                        uint64_t* n_records, uint64_t* good_bad_pairs, float* device_ms);
+/* start: n_reads + 2 entries (as mg_copy_discoveries), the list of read A =
+ * out[start[A] .. start[A+1]) in addMatePair's order; out: cap records.  Either
+ * may be NULL.  Fails unless mg_build_mate_pairs ran for the current reads. */
+int mg_copy_mate_pairs(mg_ctx* ctx, uint64_t* start, mg_mate* out, uint64_t cap, uint64_t* n_copied);
+
 /* --- sharding (multi-GPU, one process per GPU) ---------------------------- */
 /* Restrict this context to index buckets owned by `rank` of `nranks`
  * (bucket-range sharding) and/or to the source reads with

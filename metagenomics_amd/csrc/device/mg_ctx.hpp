@@ -1,7 +1,8 @@
 // mg_ctx.hpp — INTERNAL: the device context behind include/mg_overlap.h,
 // shared by the kernel translation units (mg_kernels.hip: index + discovery +
 // exchange; mg_dataset.hip: Dataset ingest on the device; mg_disc.hip: the
-// per-read discovery lists D(A)).
+// per-read discovery lists D(A); mg_comp.hip: their components; mg_mates.hip:
+// read lookup and the per-read mate lists).
 #ifndef MG_CTX_HPP_
 #define MG_CTX_HPP_
 #include <hip/hip_runtime.h>
@@ -372,6 +373,15 @@ struct mg_ctx {
   mg_comp* d_comp = nullptr;  // the table, ascending root
   size_t comp_cap = 0;
   hipEvent_t comp_ev[2] = {};
+  // per-read mate lists (mg_mates.hip, mg_build_mate_pairs): one CSR of mg_mate
+  // records over the reads; mates_ready until new reads arrive (reset_derived)
+  bool mates_ready = false;
+  uint64_t n_mates = 0;
+  uint64_t* d_mate_start = nullptr;  // start[A] (n + 2)
+  size_t mate_start_cap = 0;
+  mg_mate* d_mates = nullptr;
+  size_t mates_cap = 0;
+  hipEvent_t mate_ev[2] = {};
 };
 
 #define MG_TRY(expr)                                                                  \
@@ -470,7 +480,19 @@ inline void reset_derived(mg_ctx* ctx) {
   ctx->rows_found = false;
   ctx->disc_ready = false;
   ctx->comp_ready = false;
+  ctx->mates_ready = false;
 }
+
+// mg_dataset.hip: the ingest's per-record stage alone (k_ingest / k_ingest_long
+// over device-resident ASCII records): testRead, the canonical strand packed
+// into cw words per record, and fwd[i] = 1 when record i is its own canonical
+// string (forward strand chosen, or both strands equal).  cw =
+// ingest_record_words(longest record that can pass the length bounds).
+uint32_t ingest_record_words(uint64_t longest);
+int ingest_records(mg_ctx* ctx, const char* d_ascii, const uint64_t* d_off, uint64_t n, uint32_t min_overlap,
+                   uint32_t cw, uint64_t* canon, uint16_t* len, uint8_t* valid, uint8_t* fwd);
+// mg_mates.hip: frees the mate-list buffers (mg_destroy)
+void mates_release(mg_ctx* ctx);
 
 // mg_disc.hip: frees the discovery-list buffers (mg_destroy)
 void disc_release(mg_ctx* ctx);

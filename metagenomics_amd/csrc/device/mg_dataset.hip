@@ -66,7 +66,8 @@ __device__ __forceinline__ uint32_t base_code(const IngestSrc& s, uint64_t i, ui
 template <int W, bool ASCII>
 __global__ __launch_bounds__(kThreads) void k_ingest(IngestSrc s, uint64_t n, uint32_t min_overlap,
                                                      uint64_t* __restrict__ canon, uint16_t* __restrict__ len_out,
-                                                     uint8_t* __restrict__ valid, unsigned int* __restrict__ lenrange) {
+                                                     uint8_t* __restrict__ valid, unsigned int* __restrict__ lenrange,
+                                                     uint8_t* __restrict__ fwd_out) {
   const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   const uint64_t L = raw_len<ASCII>(s, i);
@@ -113,6 +114,7 @@ __global__ __launch_bounds__(kThreads) void k_ingest(IngestSrc s, uint64_t n, ui
   }
 #pragma unroll
   for (int k = 0; k < W; ++k) canon[i * W + k] = fwd ? f[k] : r[k];
+  if (fwd_out) fwd_out[i] = (fwd || !decided) ? 1 : 0;  // the record is the stored string itself (mg_mates.hip)
   atomicMin(&lenrange[0], (unsigned int)L);
   atomicMax(&lenrange[1], (unsigned int)L);
 }
@@ -126,7 +128,8 @@ template <bool ASCII>
 __global__ __launch_bounds__(kThreads) void k_ingest_long(IngestSrc s, uint64_t n, uint32_t min_overlap, uint32_t cw,
                                                           uint64_t* __restrict__ canon, uint16_t* __restrict__ len_out,
                                                           uint8_t* __restrict__ valid,
-                                                          unsigned int* __restrict__ lenrange) {
+                                                          unsigned int* __restrict__ lenrange,
+                                                          uint8_t* __restrict__ fwd_out) {
   const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   const uint64_t L = raw_len<ASCII>(s, i);
@@ -154,15 +157,17 @@ __global__ __launch_bounds__(kThreads) void k_ingest_long(IngestSrc s, uint64_t 
     }
     return x;
   };
-  bool fwd = false;
+  bool fwd = false, decided = false;
   for (uint32_t k = 0; 32u * k < L; ++k) {
     const uint64_t f = word(k, false), r = word(k, true);
     if (f != r) {
       fwd = f < r;
+      decided = true;
       break;
     }
   }
   for (uint32_t k = 0; k < cw; ++k) canon[i * cw + k] = 32u * k < L ? word(k, !fwd) : 0ull;
+  if (fwd_out) fwd_out[i] = (fwd || !decided) ? 1 : 0;
   atomicMin(&lenrange[0], (unsigned int)L);
   atomicMax(&lenrange[1], (unsigned int)L);
 }
@@ -266,16 +271,16 @@ struct Ingest {
     if (n) {
       if (W == 0 && ascii)
         hipLaunchKernelGGL((k_ingest_long<true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, CW,
-                           canon.p, len.p, valid.p, lr.p);
+                           canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       else if (W == 0)
         hipLaunchKernelGGL((k_ingest_long<false>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, CW,
-                           canon.p, len.p, valid.p, lr.p);
+                           canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       else if (ascii)
         hipLaunchKernelGGL((k_ingest<(W ? W : 1), true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap,
-                           canon.p, len.p, valid.p, lr.p);
+                           canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       else
         hipLaunchKernelGGL((k_ingest<(W ? W : 1), false>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap,
-                           canon.p, len.p, valid.p, lr.p);
+                           canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       MG_TRY(hipGetLastError());
     }
     // indices of the valid reads, in input order
@@ -392,7 +397,48 @@ int ingest(mg_ctx* ctx, const IngestSrc& s, bool ascii, uint64_t n, uint64_t max
   return set_err(ctx, "unsupported read length");
 }
 
+template <int W>
+void launch_records(hipStream_t st, const IngestSrc& s, uint64_t n, uint32_t min_overlap, uint64_t* canon,
+                    uint16_t* len, uint8_t* valid, unsigned int* lr, uint8_t* fwd) {
+  hipLaunchKernelGGL((k_ingest<W, true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, canon, len, valid,
+                     lr, fwd);
+}
+
 }  // namespace
+
+uint32_t ingest_record_words(uint64_t longest) {
+  const uint64_t need = std::max<uint64_t>(1, (std::min<uint64_t>(longest, 65535) + 31) / 32);
+  return need > 32 ? (uint32_t)need : supported_maxw((uint32_t)need);
+}
+
+int ingest_records(mg_ctx* ctx, const char* d_ascii, const uint64_t* d_off, uint64_t n, uint32_t min_overlap,
+                   uint32_t cw, uint64_t* canon, uint16_t* len, uint8_t* valid, uint8_t* fwd) {
+  if (!n) return 0;
+  hipStream_t st = ctx->stream;
+  DevBuf<unsigned int> lr;  // the kernels' length range: not used here
+  MG_TRY(lr.alloc(2));
+  MG_TRY(hipMemsetAsync(lr.p, 0, 2 * sizeof(unsigned int), st));
+  const IngestSrc s{d_ascii, d_off, nullptr, 0, nullptr};
+  switch (cw) {
+    case 1: launch_records<1>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 2: launch_records<2>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 3: launch_records<3>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 4: launch_records<4>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 5: launch_records<5>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 6: launch_records<6>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 8: launch_records<8>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 12: launch_records<12>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 16: launch_records<16>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    case 32: launch_records<32>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
+    default:
+      if (cw < 33) return set_err(ctx, "unsupported record width");
+      hipLaunchKernelGGL((k_ingest_long<true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, cw, canon,
+                         len, valid, lr.p, fwd);
+  }
+  MG_TRY(hipGetLastError());
+  MG_TRY(hipStreamSynchronize(st));  // (lr is freed on return)
+  return 0;
+}
 
 extern "C" {
 

@@ -4001,6 +4001,7 @@ void mg_destroy(mg_ctx* ctx) {
     if (b) (void)hipFree(b);
   disc_release(ctx);
   comp_release(ctx);
+  mates_release(ctx);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);

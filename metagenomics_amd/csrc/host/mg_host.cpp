@@ -17,6 +17,7 @@
 #include <unordered_map>
 
 #include "mg_api.hpp"
+#include "mg_mates.hpp"
 #include "mg_parse.hpp"
 #include "mg_unitig.hpp"
 #include "mg_graph.hpp"
@@ -349,6 +350,11 @@ std::string Read::getStringForward() { return owner->decode(readNumber, false); 
 std::string Read::getStringReverse() { return owner->decode(readNumber, true); }
 UINT16 Read::getReadLength() { return owner->packedLengths()[readNumber - 1]; }
 UINT32 Read::getFrequency() { return owner->frequencyOf(readNumber); }
+MatePairList Read::getMatePairList() {
+  if (owner->mateStart.empty()) return MatePairList(nullptr, nullptr);
+  const MPlist* base = owner->mates.data();
+  return MatePairList(base + owner->mateStart[readNumber], base + owner->mateStart[readNumber + 1]);
+}
 
 // =============================================================== Dataset ====
 Dataset::Dataset(std::vector<std::string> pe, std::vector<std::string> se, UINT64 minOverlap)
@@ -452,6 +458,48 @@ Read* Dataset::getReadFromString(const std::string& read) {
       hi = mid;
   }
   throw mg::Error("String not found in Dataset: " + read);
+}
+
+void Dataset::readMatePairsFromFile() {
+  // Dataset.cpp:97-104: storeMatePairInformation(file i, minimumOverlapLength, i)
+  if (pairedEndDatasetFileNames.empty()) return;
+  std::string text;
+  std::vector<uint64_t> off{0}, ppd;
+  for (const auto& f : pairedEndDatasetFileNames) {
+    uint64_t np = 0;
+    const int rc = mg::read_pairs_file(f, text, off, &np);  // :208-267
+    if (rc == -1) throw mg::Error("Unable to open file: " + f);
+    if (rc) throw mg::Error("Unknown input file format: " + f);
+    ppd.push_back(np);
+  }
+  if (ppd.size() > 256) throw mg::Error("more than 256 paired-end files (datasetNumber is UINT8)");
+  const uint64_t n_raw = off.size() - 1, N = numberOfUniqueReads;
+  const char* env = std::getenv("MG_DEVICE_MATES");
+  const bool device = mateCtx && !(env && *env && std::atoi(env) == 0);
+  std::vector<uint64_t> start(N + 2, 0);
+  std::vector<mg_mate> recs;
+  if (device) {  // the context holds this Dataset's reads and its superReadIDs (markContainedReads ran)
+    uint64_t n = 0, got = 0;
+    if (mg_build_mate_pairs(mateCtx, text.data(), off.data(), n_raw, ppd.data(), (uint32_t)ppd.size(),
+                            (uint32_t)minOverlapLength, 1, &n, nullptr, nullptr))
+      mg::fail(mateCtx, "readMatePairsFromFile");
+    recs.resize(n);
+    if (mg_copy_mate_pairs(mateCtx, start.data(), recs.data(), n, &got) || got != n)
+      mg::fail(mateCtx, "readMatePairsFromFile");
+  } else {
+    std::vector<uint32_t> super(N + 1, 0);
+    for (UINT64 i = 1; i <= N; ++i) super[i] = (uint32_t)reads[i - 1].superReadID;
+    mg::MatePairs mp;
+    std::string err;
+    if (mp.build(packed->words.data(), packed->lens.data(), N, packed->wpr, super.data(), text.data(), off.data(),
+                 n_raw, ppd.data(), (uint32_t)ppd.size(), (uint32_t)minOverlapLength, &err))
+      throw mg::Error("readMatePairsFromFile: " + err);
+    start.swap(mp.start);
+    recs.swap(mp.recs);
+  }
+  mateStart.swap(start);
+  mates.resize(recs.size());
+  for (size_t k = 0; k < recs.size(); ++k) mates[k] = MPlist{recs[k].id, recs[k].orient, recs[k].dataset};
 }
 
 void Dataset::saveReads(std::string fileName) {
@@ -773,6 +821,21 @@ bool discoveries_of(mg_ctx* ctx, uint64_t nrows, const uint16_t* lens, UINT64 N,
 }
 }  // namespace
 
+namespace {
+// dataSet->readMatePairsFromFile() with the build's device context at hand
+// (the context dies with the HashTable, so it is lent for this call only)
+void mate_pairs_on(Dataset* ds, mg_ctx** slot, mg_ctx* ctx) {
+  *slot = ctx;
+  try {
+    ds->readMatePairsFromFile();
+  } catch (...) {
+    *slot = nullptr;
+    throw;
+  }
+  *slot = nullptr;
+}
+}  // namespace
+
 void OverlapGraph::setDeviceDiscoveries(bool on) { g_device_disc = on ? 1 : 0; }
 void OverlapGraph::setDeviceComponents(bool on) { g_device_comp = on ? 1 : 0; }
 
@@ -789,6 +852,7 @@ bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
   for (UINT64 i = 0; i <= N; ++i) graph->push_back(new std::vector<Edge*>());
   markContainedReads();
   mg_ctx* ctx = ht->context();
+  mate_pairs_on(dataSet, &dataSet->mateCtx, ctx);  // OverlapGraph.cpp:142
   uint64_t nrows = 0;
   if (mg_find_overlaps(ctx, &nrows)) mg::fail(ctx, "buildOverlapGraphFromHashTable");
   mg_get_timings(ctx, &lastTimings);
@@ -848,6 +912,7 @@ bool OverlapGraph::beginBuildFromHashTable(HashTable* ht) {
   for (UINT64 i = 0; i <= N; ++i) graph->push_back(new std::vector<Edge*>());
   markContainedReads();
   mg_ctx* ctx = ht->context();
+  mate_pairs_on(dataSet, &dataSet->mateCtx, ctx);  // OverlapGraph.cpp:142
   uint64_t nrows = 0;
   if (mg_find_overlaps(ctx, &nrows)) mg::fail(ctx, "beginBuildFromHashTable");
   mg_get_timings(ctx, &lastTimings);

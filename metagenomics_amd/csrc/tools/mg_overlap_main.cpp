@@ -15,6 +15,11 @@
 //                readGraphFromFile(<prefix>.unitig) -> sortEdges (no device
 //                needed), then saveGraphToFile(<prefix>.resumed.unitig) and the
 //                lists in list order to <prefix>.resumed.graph.
+//   -mates       also write every Read::getMatePairList() (filled from the -pe
+//                files by readMatePairsFromFile, OverlapGraph.cpp:142 and
+//                OverlapGraph.h:79) as "#M read mate orient dataset" lines, reads
+//                in ID order, entries in list order, to <prefix>.mates (with -s:
+//                <prefix>.resumed.mates);
 //   -xchg <K>    the exchange mode over RCCL: one
 //                process per GPU (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR /
 //                MASTER_PORT as torchrun --no-python sets them; none set = one
@@ -221,9 +226,21 @@ static int run_xchg_sim(Dataset* ds, int dev, int P, XchgOpts o) {
   return rc;
 }
 
+static void save_mates(Dataset* ds, const std::string& path) {
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) throw std::runtime_error("Unable to open file: " + path);
+  for (UINT64 i = 1; i <= ds->getNumberOfUniqueReads(); ++i) {
+    const MatePairList l = ds->getReadFromID(i)->getMatePairList();
+    for (size_t j = 0; j < l->size(); ++j)
+      std::fprintf(f, "#M %llu %llu %d %d\n", i, l->at(j).matePairID, (int)l->at(j).matePairOrientation,
+                   (int)l->at(j).datasetNumber);
+  }
+  std::fclose(f);
+}
+
 static void usage() {
   std::fprintf(stderr,
-               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-nocontract | -raw | -s | -xchg K "
+               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-nocontract | -raw | -s | -xchg K "
                "[-xchg-sim P] [-xchg-caps F]]\n");
 }
 
@@ -232,7 +249,7 @@ int main(int argc, char** argv) {
   std::string prefix;
   unsigned long long l = 0;
   int k = 0, dev = 0;
-  bool raw = false, nocontract = false, resume = false;
+  bool raw = false, nocontract = false, resume = false, mates = false;
   int xchg_steps = -1, xchg_sim = 0;
   double xchg_caps = 1.0;
   for (int i = 1; i < argc; ++i) {
@@ -254,6 +271,8 @@ int main(int argc, char** argv) {
       nocontract = true;
     } else if (a == "-s") {
       resume = true;
+    } else if (a == "-mates") {
+      mates = true;
     } else if (a == "-xchg" && i + 1 < argc) {
       xchg_steps = std::max(0, std::atoi(argv[++i]));
     } else if (a == "-xchg-sim" && i + 1 < argc) {
@@ -292,6 +311,7 @@ int main(int argc, char** argv) {
       g->sortEdges();
       g->saveGraphToFile(prefix + ".resumed.unitig");
       g->saveGraphLists(prefix + ".resumed.graph");
+      if (mates) save_mates(ds, prefix + ".resumed.mates");
       std::printf("{\"unique_reads\": %llu, \"nodes\": %llu, \"directed_edges\": %llu}\n",
                   (unsigned long long)ds->getNumberOfUniqueReads(), (unsigned long long)g->getNumberOfNodes(),
                   (unsigned long long)g->getNumberOfEdges());
@@ -303,6 +323,7 @@ int main(int argc, char** argv) {
     ht->insertDataset(ds, l);
     OverlapGraph* g = new OverlapGraph(ht);  // deletes ht
     ds->saveReads(prefix + "_sortedReads.fasta");
+    if (mates) save_mates(ds, prefix + ".mates");
     if (raw) {
       g->saveRawEdges(prefix + ".edges");
     } else if (nocontract) {

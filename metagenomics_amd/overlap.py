@@ -26,6 +26,8 @@ EDGE_DTYPE = np.dtype([("src", "<u4"), ("dst", "<u4"), ("offset", "<u2"), ("orie
 DISC_DTYPE = np.dtype([("dst", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("o", "u1")])
 # one connected component of the discovery lists (mg_comp, include/mg_overlap.h): 16 bytes
 COMP_DTYPE = np.dtype([("root", "<u4"), ("n_reads", "<u4"), ("n_disc", "<u4"), ("n_self", "<u4")])
+# one entry of a read's mate list (mg_mate, include/mg_overlap.h): 8 bytes
+MATE_DTYPE = np.dtype([("id", "<u4"), ("orient", "u1"), ("dataset", "u1"), ("pad", "<u2")])
 
 
 class MgError(RuntimeError):
@@ -88,6 +90,9 @@ def lib() -> C.CDLL:
         "mg_copy_discoveries": (i32, [vp, vp, vp, u64, P(u64)]),
         "mg_build_components": (i32, [vp, P(u64), P(C.c_float)]),
         "mg_copy_components": (i32, [vp, vp, vp, u64, P(u64)]),
+        "mg_find_reads": (i32, [vp, C.c_char_p, vp, u64, u32, vp, vp, P(C.c_float)]),
+        "mg_build_mate_pairs": (i32, [vp, C.c_char_p, vp, u64, vp, u32, u32, i32, P(u64), vp, P(C.c_float)]),
+        "mg_copy_mate_pairs": (i32, [vp, vp, vp, u64, P(u64)]),
         "mg_set_shard": (i32, [vp, u32, u32, u64, u64]),
         "mg_get_timings": (i32, [vp, P(_Timings)]),
         "mg_get_counters": (i32, [vp, P(_Counters)]),
@@ -136,6 +141,10 @@ def lib() -> C.CDLL:
         "mgh_parse_files": (i32, [P(C.c_char_p), i32, i32, P(vp), P(vp), P(u64), P(C.c_double)]),
         "mgh_parse_buffer": (i32, [vp, u64, i32, P(vp), P(vp), P(u64), P(C.c_double)]),
         "mgh_parse_free": (None, [vp]),
+        "mgh_read_pairs": (i32, [P(C.c_char_p), i32, P(vp), P(vp), P(u64), vp, P(C.c_double)]),
+        "mgh_read_pairs_buffer": (i32, [vp, u64, P(vp), P(vp), P(u64)]),
+        "mgh_mate_pairs_build": (i32, [vp, vp, u64, u32, vp, C.c_char_p, vp, u64, vp, u32, u32, vp, vp, u64, P(u64),
+                                       vp, P(i64)]),
         "mgh_parse_set_min_chunk": (None, [u64]),
         "mgh_graph_contract": (i32, [vp, i32, P(u64), P(u64), P(u64)]),
         "mgh_graph_read_unitig": (i32, [C.c_char_p, vp, u64, P(vp)]),
@@ -453,6 +462,69 @@ class OverlapEngine:
         self._check(lib().mg_copy_discoveries(self._h, _ptr(start), _ptr(disc), n, C.byref(got)), "copy_discoveries")
         return start, disc[: got.value]
 
+    # --- read lookup and mate pairs
+    @staticmethod
+    def _records(seqs, text, offsets):
+        if text is None:
+            text = "".join(seqs).encode()
+            offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            offsets[1:] = np.cumsum([len(s) for s in seqs])
+        return text, np.ascontiguousarray(offsets, dtype=np.uint64)
+
+    def find_reads(self, seqs: Sequence[str] | None = None, min_overlap: int = 0, text: bytes | None = None,
+                   offsets: np.ndarray | None = None):
+        """mg_find_reads: Dataset::getReadFromString for a batch of raw records
+        (any case), over the resident reads.  Returns (ids uint32, flags uint8):
+        ids[i] = the ID of the read equal to the record's canonical string, 0
+        when the record fails the ingest's filter or no read equals it; flags
+        bit 0 = passed the filter, bit 1 = the record itself is the stored
+        string.  find_ms keeps the device time."""
+        text, offsets = self._records(seqs, text, offsets)
+        n = offsets.shape[0] - 1
+        ids = np.zeros(n, dtype=np.uint32)
+        flags = np.zeros(n, dtype=np.uint8)
+        ms = C.c_float()
+        self._check(lib().mg_find_reads(self._h, text, _ptr(offsets), n, min_overlap, _ptr(ids), _ptr(flags),
+                                        C.byref(ms)), "find_reads")
+        self.find_ms = float(ms.value)
+        return ids, flags
+
+    def build_mate_pairs(self, text: bytes, offsets: np.ndarray, pairs_per_dataset, min_overlap: int,
+                         use_super: bool = True) -> int:
+        """mg_build_mate_pairs over parsed pairs (records 2p, 2p + 1 = pair p).
+        Returns the total list length; mates_ms, good_pairs, bad_pairs keep
+        the device time and the pair counts."""
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ppd = np.ascontiguousarray(pairs_per_dataset, dtype=np.uint64)
+        n, ms = C.c_uint64(), C.c_float()
+        gb = np.zeros(2, dtype=np.uint64)
+        self._n_mates = 0
+        rc = lib().mg_build_mate_pairs(self._h, text, _ptr(offsets), offsets.shape[0] - 1, _ptr(ppd), ppd.shape[0],
+                                       min_overlap, int(bool(use_super)), C.byref(n), _ptr(gb), C.byref(ms))
+        self.good_pairs, self.bad_pairs = int(gb[0]), int(gb[1])
+        self._check(rc, "build_mate_pairs")
+        self.mates_ms = float(ms.value)
+        self._n_mates = int(n.value)
+        return self._n_mates
+
+    def mate_lists(self):
+        """(start uint64[n_reads + 2], records[MATE_DTYPE]): the mate list of read
+        A = records[start[A]:start[A + 1]] in addMatePair's order."""
+        n = getattr(self, "_n_mates", 0)
+        start = np.zeros(int(lib().mg_num_reads(self._h)) + 2, dtype=np.uint64)
+        recs = np.zeros(n, dtype=MATE_DTYPE)
+        got = C.c_uint64()
+        self._check(lib().mg_copy_mate_pairs(self._h, _ptr(start), _ptr(recs), n, C.byref(got)), "copy_mate_pairs")
+        return start, recs[: got.value]
+
+    def mate_pairs(self, files: Sequence[str], min_overlap: int, use_super: bool = True):
+        """storeMatePairInformation of the paired-end `files` on the device:
+        the serial pair reader (mgh_read_pairs), then mg_build_mate_pairs and
+        mg_copy_mate_pairs.  Returns (start, records)."""
+        text, offsets, ppd, _ = read_pairs(files)
+        self.build_mate_pairs(text, offsets, ppd, min_overlap, use_super)
+        return self.mate_lists()
+
     # --- connected components of the lists, labelled on the device
     def build_components(self) -> int:
         """mg_build_components: label every read with the smallest read ID its
@@ -682,6 +754,60 @@ def replay_discoveries(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, mi
         return int(L.mgh_graph_nodes(g)), int(L.mgh_graph_edges(g)), out
     finally:
         L.mgh_graph_free(g)
+
+
+def read_pairs(files: Sequence[str] | None = None, data: bytes | None = None):
+    """The mates of every pair as storeMatePairInformation's loop reads them
+    (mgh_read_pairs; `data`: one file's bytes).  Returns (text bytes, offsets
+    uint64[n + 1], pairs_per_file uint64, seconds): records 2p, 2p + 1 = pair p."""
+    L = lib()
+    t, o, n, sec = C.c_void_p(), C.c_void_p(), C.c_uint64(), C.c_double()
+    if data is not None:
+        ppf = np.zeros(1, dtype=np.uint64)
+        buf = np.frombuffer(data, dtype=np.uint8)
+        rc = L.mgh_read_pairs_buffer(_ptr(buf) if len(data) else None, len(data), C.byref(t), C.byref(o), C.byref(n))
+    else:
+        ppf = np.zeros(len(files), dtype=np.uint64)
+        arr = (C.c_char_p * len(files))(*[os.fsencode(f) for f in files])
+        rc = L.mgh_read_pairs(arr, len(files), C.byref(t), C.byref(o), C.byref(n), _ptr(ppf), C.byref(sec))
+    if rc:
+        raise MgError({-1: "Unable to open file", -2: "Unknown input file format."}.get(rc, f"read_pairs failed ({rc})"))
+    try:
+        offsets = np.ctypeslib.as_array(C.cast(o, C.POINTER(C.c_uint64)), shape=(n.value + 1,)).copy()
+        text = C.string_at(t, int(offsets[-1]))
+    finally:
+        L.mgh_parse_free(t)
+        L.mgh_parse_free(o)
+    if data is not None:
+        ppf[0] = n.value // 2
+    return text, offsets, ppf, sec.value
+
+
+def host_mate_pairs(words: np.ndarray, lens: np.ndarray, text: bytes, offsets: np.ndarray, pairs_per_dataset,
+                    min_overlap: int, super_ids: np.ndarray | None = None):
+    """mg::MatePairs::build (mgh_mate_pairs_build): the host mirror of
+    build_mate_pairs + mate_lists, on the CPU.  super_ids = superReadID per ID
+    (n + 1 entries) or None (all 0).  Returns (start, records, good, bad)."""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+    ppd = np.ascontiguousarray(pairs_per_dataset, dtype=np.uint64)
+    n = lens.shape[0]
+    wpr = words.shape[1] if words.ndim == 2 else 1
+    n_raw = offsets.shape[0] - 1
+    sup = None if super_ids is None else np.ascontiguousarray(super_ids, dtype=np.uint32)
+    start = np.zeros(n + 2, dtype=np.uint64)
+    recs = np.zeros(n_raw, dtype=MATE_DTYPE)
+    cnt, nf = C.c_uint64(), C.c_int64()
+    gb = np.zeros(2, dtype=np.uint64)
+    rc = lib().mgh_mate_pairs_build(_ptr(words), _ptr(lens), n, wpr, None if sup is None else _ptr(sup), text,
+                                    _ptr(offsets), n_raw, _ptr(ppd), ppd.shape[0], min_overlap, _ptr(start),
+                                    _ptr(recs), n_raw, C.byref(cnt), _ptr(gb), C.byref(nf))
+    if rc == -2:
+        raise MgError(f"String not found in Dataset: raw record {nf.value}")
+    if rc:
+        raise MgError(f"host_mate_pairs: bad arguments ({rc})")
+    return start, recs[: cnt.value], int(gb[0]), int(gb[1])
 
 
 def _parse_result(L, rc, t, o, n, what):
