@@ -137,6 +137,7 @@ class Edge {
   std::vector<UINT8>* getListOfOrientations() { return &listOfOrientations; }
   bool transitiveRemovalFlag = false;
   UINT16 flow = 0;  // Edge.h:42 (0 until flow is computed)
+  UINT64 coverageDepth = 0;  // Edge.h:43 (0 until flow is computed)
 
  private:
   friend class OverlapGraph;
@@ -295,6 +296,21 @@ class OverlapGraph {
   UINT64 removeDeadEndNodes();
   void sortEdges();                                // :2799-2808
   bool saveGraphToFile(const std::string& fileName);  // the .unitig checkpoint (:1219-1261)
+  // getStringInEdge (:2009-2041): the sequence the edge spells, by the host
+  // mirror (mg::contigs_build); where the reference's substr would throw this
+  // throws std::out_of_range naming the piece
+  std::string getStringInEdge(Edge* edge);
+  // printGraph (:428-520): the .gdl file and the contigs as FASTA (main.cpp:55
+  // passes <prefix>graph1.gdl, <prefix>contigs1.fasta); the cout statistics
+  // (:495-514) are not reproduced.  The strings of all contigs are built on the
+  // device in one call (mg_build_contigs): in the hash table's context while a
+  // caller-driven build still holds one, else (new OverlapGraph(ht) has freed
+  // the table, :210) in a context of its own that uploads the Dataset's packed
+  // reads.  Without a HIP device, or with device contigs off, the host mirror
+  // spells them.  The same two files either way.
+  bool printGraph(std::string graphFileName, std::string contigFileName);
+  // Until this is called the environment variable MG_DEVICE_CONTIGS decides (0 = host mirror).
+  static void setDeviceContigs(bool on);
   const mg_timings& timings() const { return lastTimings; }
 
  private:

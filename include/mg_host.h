@@ -212,6 +212,42 @@ uint64_t mgh_graph_unitig_edges(const mgh_graph* g, mgh_unitig_edge* edges, uint
                                 uint64_t* read_start, uint32_t* reads, uint16_t* offs, uint8_t* ors,
                                 uint64_t read_cap, uint64_t* n_reads_total);
 
+/* --- contig sequences: getStringInEdge + printGraph (OverlapGraph.cpp:2009-2041, 428-520)
+ * The edges of a contracted or re-read handle as mg_build_contigs /
+ * mgh_contigs_build take them (mg_contig_edge, include/mg_overlap.h), in u
+ * order, each list in list order, `tail` filled from the reverse edge, with
+ * their read lists gathered into reads / offs / ors (`first` indexes those).
+ * all = 0: printGraph's contigs only, in its selection order (:460): src < dst,
+ * and of a self-loop pair the edge created first (the rule mgh_graph_save_unitig
+ * uses for the reference's pointer compare); all != 0: every edge.  Any output
+ * may be NULL.  Returns the number of edges; *n_list the length of the lists.
+ * Edges beyond edge_cap or list entries beyond list_cap are not written. */
+uint64_t mgh_graph_contig_edges(const mgh_graph* g, int all, mg_contig_edge* edges, uint64_t edge_cap,
+                                uint32_t* reads, uint16_t* offs, uint8_t* ors, uint64_t list_cap, uint64_t* n_list);
+/* The host mirror of mg_build_contigs + mg_copy_contigs on packed words (ID
+ * order, words_per_read words each): the definition of the pieces, in
+ * O(output).  start: n_edges + 1 entries; out: cap bytes, written only when cap
+ * >= the total; either may be NULL.  *total = length of all strings.  0 = ok;
+ * -1 = bad arguments; -2 = an invalid piece or a read ID outside 1..n_reads:
+ * err (err_cap bytes, NUL-terminated, optional) names the first such edge and
+ * piece, and nothing is read out of range. */
+int mgh_contigs_build(const uint64_t* words, const uint16_t* lens, uint64_t n_reads, uint32_t words_per_read,
+                      const mg_contig_edge* edges, uint64_t n_edges, const uint32_t* reads, const uint16_t* offs,
+                      const uint8_t* ors, uint64_t n_list, uint64_t* start, char* out, uint64_t cap, uint64_t* total,
+                      char* err, uint64_t err_cap);
+/* printGraph (:428-520) of a contracted or re-read handle: the .gdl file byte
+ * for byte (header block, node lines, one edge line per contig, "}" without a
+ * newline) and the contigs as FASTA, sorted by std::sort with compareEdges
+ * (offset) and reversed, headers as :484 writes them (Flow and Coverage are 0
+ * until flow exists), 100 bases per line.  start / strings: the strings of the
+ * contigs in mgh_graph_contig_edges(all = 0) order as a device built them
+ * (mg_copy_contigs), or NULL: the mirror spells them from words / lens.  The
+ * cout statistics (:495-514) are not reproduced.  0 = ok; -1 = bad arguments or
+ * a file cannot be written; -2 = an invalid piece (err as above). */
+int mgh_graph_print(const mgh_graph* g, const uint64_t* words, const uint16_t* lens, uint64_t n_reads,
+                    uint32_t words_per_read, const uint64_t* start, const char* strings, const char* gdl_path,
+                    const char* fasta_path, char* err, uint64_t err_cap);
+
 #ifdef __cplusplus
 }
 #endif

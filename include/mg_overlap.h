@@ -270,6 +270,47 @@ int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets
  * may be NULL.  Fails unless mg_build_mate_pairs ran for the current reads. */
 int mg_copy_mate_pairs(mg_ctx* ctx, uint64_t* start, mg_mate* out, uint64_t cap, uint64_t* n_copied);
 
+/* --- contig sequences (OverlapGraph::getStringInEdge, OverlapGraph.cpp:2009-2041)
+ * One edge whose string is to be spelled.  Its reads / offsets / orientations
+ * (listOfReads, listOfOverlapOffsets, listOfOrientations) are entries
+ * [first, first + n) of the shared lists; tail = the reverse edge's
+ * listOfOverlapOffsets[0] (read only when n > 0).  40 bytes. */
+typedef struct mg_contig_edge {
+  uint32_t src, dst; /* read IDs */
+  uint64_t offset;   /* getOverlapOffset */
+  uint64_t first;
+  uint32_t n;
+  uint32_t tail;
+  uint8_t orient, pad[7];
+} mg_contig_edge;
+/* The string of edge k is n + 2 pieces laid end to end:
+ *   piece 0      the whole source read, forward strand iff orient is 2 or 3;
+ *   piece i + 1  reads[first + i], forward strand iff ors[first + i] == 1: with
+ *                prev = the length of the previous piece's read, the bases of
+ *                that strand from position prev - offs[first + i] on, preceded
+ *                by 'N' iff offs[first + i] == prev;
+ *   tail         the destination read, forward strand iff orient is 1 or 3, from
+ *                position len(src) - offset (n == 0) or len(dst) - tail on.
+ * A piece is valid iff its position lies in [0, length of its read] (std::string::
+ * substr throws otherwise); an empty piece is valid.  All pieces of all edges are
+ * sized by one kernel, placed by one 64-bit exclusive scan and written by one
+ * copy kernel that reads each piece's read from the resident packed reads (the
+ * reverse strand is derived in registers).  Needs only a context that holds the
+ * reads (any upload or ingest, either slot layout, any width, long reads
+ * included); no index.  *total_bases = the length of all strings together;
+ * *device_ms (optional) = HIP-event time of the kernels (no transfers).
+ * Errors: -1 (bad arguments, a context without reads, a list range outside
+ * n_list, a HIP error); -2 an invalid piece or a read ID outside 1..n_reads: no
+ * copy kernel runs and mg_last_error names the first such edge and piece.  The
+ * strings stay on the device until the next upload or ingest. */
+int mg_build_contigs(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edges, const uint32_t* reads,
+                     const uint16_t* offs, const uint8_t* ors, uint64_t n_list, uint64_t* total_bases,
+                     float* device_ms);
+/* start: n_edges + 1 entries, the string of edge k = out[start[k] .. start[k+1])
+ * (ASCII, no terminator); out: cap bytes.  Either may be NULL.  Fails unless
+ * mg_build_contigs succeeded for the current reads. */
+int mg_copy_contigs(mg_ctx* ctx, uint64_t* start, char* out, uint64_t cap, uint64_t* n_copied);
+
 /* --- sharding (multi-GPU, one process per GPU) ---------------------------- */
 /* Restrict this context to index buckets owned by `rank` of `nranks`
  * (bucket-range sharding) and/or to the source reads with

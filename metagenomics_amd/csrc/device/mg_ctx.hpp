@@ -2,7 +2,7 @@
 // shared by the kernel translation units (mg_kernels.hip: index + discovery +
 // exchange; mg_dataset.hip: Dataset ingest on the device; mg_disc.hip: the
 // per-read discovery lists D(A); mg_comp.hip: their components; mg_mates.hip:
-// read lookup and the per-read mate lists).
+// read lookup and the per-read mate lists; mg_contigs.hip: the strings of edges).
 #ifndef MG_CTX_HPP_
 #define MG_CTX_HPP_
 #include <hip/hip_runtime.h>
@@ -382,6 +382,30 @@ struct mg_ctx {
   mg_mate* d_mates = nullptr;
   size_t mates_cap = 0;
   hipEvent_t mate_ev[2] = {};
+  // contig strings (mg_contigs.hip, mg_build_contigs): one descriptor and one
+  // output position per piece, the edges' string starts and the ASCII bases;
+  // contigs_ready until new reads arrive (reset_derived)
+  bool contigs_ready = false;
+  uint64_t n_contig_edges = 0, n_contig_bases = 0;
+  uint64_t* d_ctg_desc = nullptr;  // per piece: slot | position << 32 | read length << 48
+  size_t ctg_desc_cap = 0;
+  uint8_t* d_ctg_flag = nullptr;   // per piece: bit 0 forward strand, bit 1 'N' first
+  size_t ctg_flag_cap = 0;
+  uint64_t* d_ctg_len = nullptr;   // per piece: bases it writes (scan input)
+  size_t ctg_len_cap = 0;
+  uint64_t* d_ctg_pos = nullptr;   // per piece (+ 1): where it writes
+  size_t ctg_pos_cap = 0;
+  uint64_t* d_ctg_pbase = nullptr; // per edge (+ 1): its first piece
+  size_t ctg_pbase_cap = 0;
+  uint64_t* d_ctg_start = nullptr; // per edge (+ 1): where its string starts
+  size_t ctg_start_cap = 0;
+  char* d_ctg_out = nullptr;
+  size_t ctg_out_cap = 0;
+  uint8_t* d_ctg_tmp = nullptr;    // the scan's temporary storage
+  size_t ctg_tmp_cap = 0;
+  unsigned long long* d_ctg_ctl = nullptr;  // [0] = first invalid piece
+  size_t ctg_ctl_cap = 0;
+  hipEvent_t ctg_ev[2] = {};
 };
 
 #define MG_TRY(expr)                                                                  \
@@ -481,6 +505,7 @@ inline void reset_derived(mg_ctx* ctx) {
   ctx->disc_ready = false;
   ctx->comp_ready = false;
   ctx->mates_ready = false;
+  ctx->contigs_ready = false;
 }
 
 // mg_dataset.hip: the ingest's per-record stage alone (k_ingest / k_ingest_long
@@ -493,6 +518,8 @@ int ingest_records(mg_ctx* ctx, const char* d_ascii, const uint64_t* d_off, uint
                    uint32_t cw, uint64_t* canon, uint16_t* len, uint8_t* valid, uint8_t* fwd);
 // mg_mates.hip: frees the mate-list buffers (mg_destroy)
 void mates_release(mg_ctx* ctx);
+// mg_contigs.hip: frees the contig buffers (mg_destroy)
+void contigs_release(mg_ctx* ctx);
 
 // mg_disc.hip: frees the discovery-list buffers (mg_destroy)
 void disc_release(mg_ctx* ctx);

@@ -4002,6 +4002,7 @@ void mg_destroy(mg_ctx* ctx) {
   disc_release(ctx);
   comp_release(ctx);
   mates_release(ctx);
+  contigs_release(ctx);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);

@@ -17,6 +17,7 @@
 #include <unordered_map>
 
 #include "mg_api.hpp"
+#include "mg_contigs.hpp"
 #include "mg_mates.hpp"
 #include "mg_parse.hpp"
 #include "mg_unitig.hpp"
@@ -707,6 +708,83 @@ bool OverlapGraph::saveGraphToFile(const std::string& fileName) {
   adoptEdgeLists();
   if (!unitig) throw mg::Error("saveGraphToFile: no replayed graph");
   if (unitig->save_unitig(fileName.c_str())) throw mg::Error("Unable to open file: " + fileName);
+  return true;
+}
+
+namespace {
+// g_device_contigs: OverlapGraph::setDeviceContigs; -1 = not called, the
+// environment variable MG_DEVICE_CONTIGS decides (unset: device)
+int g_device_contigs = -1;
+
+bool env_device_contigs() {
+  const char* v = std::getenv("MG_DEVICE_CONTIGS");
+  return v && *v ? std::atoi(v) != 0 : true;
+}
+}  // namespace
+
+void OverlapGraph::setDeviceContigs(bool on) { g_device_contigs = on ? 1 : 0; }
+
+std::string OverlapGraph::getStringInEdge(Edge* edge) {
+  if (!edge || !dataSet) throw mg::Error("getStringInEdge: no edge / no Dataset");
+  mg_contig_edge c{};
+  c.src = (uint32_t)edge->getSourceRead()->getReadNumber();
+  c.dst = (uint32_t)edge->getDestinationRead()->getReadNumber();
+  c.offset = edge->getOverlapOffset();
+  c.n = (uint32_t)edge->getListOfReads()->size();
+  c.orient = edge->getOrientation();
+  if (c.n) c.tail = edge->getReverseEdge()->getListOfOverlapOffsets()->at(0);  // (:2037; throws as the reference's at)
+  const std::vector<uint32_t> reads(edge->getListOfReads()->begin(), edge->getListOfReads()->end());
+  std::vector<uint64_t> start;
+  std::string out, err;
+  const int rc = mg::contigs_build(dataSet->packedWords(), dataSet->packedLengths(), dataSet->getNumberOfUniqueReads(),
+                                   dataSet->wordsPerRead(), &c, 1, reads.data(), edge->getListOfOverlapOffsets()->data(),
+                                   edge->getListOfOrientations()->data(), c.n, &start, &out, &err);
+  if (rc == -2) throw std::out_of_range("getStringInEdge: " + err);
+  if (rc) throw mg::Error("getStringInEdge: " + err);
+  return out;
+}
+
+bool OverlapGraph::printGraph(std::string graphFileName, std::string contigFileName) {
+  adoptEdgeLists();
+  if (!unitig) throw mg::Error("printGraph: no replayed graph");
+  mg::ContigLists c;
+  mg::contig_edges(*unitig, false, &c);
+  const UINT64 N = dataSet->getNumberOfUniqueReads();
+  std::vector<uint64_t> start;
+  std::string bases, err;
+  const bool device = (g_device_contigs < 0 ? env_device_contigs() : g_device_contigs != 0) && N &&
+                      mg_device_count() > 0;
+  if (device) {
+    mg_ctx* held = hashTable ? hashTable->context() : nullptr;
+    if (held && mg_num_reads(held) != N) held = nullptr;
+    mg_ctx* ctx = held;
+    if (!ctx) {
+      if (mg_create(&ctx, mg::g_default_device)) throw mg::Error("printGraph: cannot create a device context");
+      if (mg_upload_reads_packed(ctx, dataSet->packedWords(), dataSet->packedLengths(), N, dataSet->wordsPerRead())) {
+        const std::string why = mg_last_error(ctx);
+        mg_destroy(ctx);
+        throw mg::Error("printGraph: upload: " + why);
+      }
+    }
+    uint64_t total = 0, copied = 0;
+    start.assign(c.edges.size() + 1, 0);
+    int rc = mg_build_contigs(ctx, c.edges.data(), c.edges.size(), c.reads.data(), c.offs.data(), c.ors.data(),
+                              c.reads.size(), &total, nullptr);
+    if (!rc) {
+      bases.resize(total);
+      rc = mg_copy_contigs(ctx, start.data(), total ? &bases[0] : nullptr, total, &copied);
+    }
+    const std::string why = rc ? mg_last_error(ctx) : "";
+    if (!held) mg_destroy(ctx);
+    if (rc) throw mg::Error("printGraph: " + why);
+  } else {
+    const int rc = mg::contigs_build(dataSet->packedWords(), dataSet->packedLengths(), N, dataSet->wordsPerRead(),
+                                     c.edges.data(), c.edges.size(), c.reads.data(), c.offs.data(), c.ors.data(),
+                                     c.reads.size(), &start, &bases, &err);
+    if (rc) throw mg::Error("printGraph: " + err);
+  }
+  if (mg::print_graph(*unitig, c, start.data(), bases.data(), graphFileName.c_str(), contigFileName.c_str()))
+    throw mg::Error("Unable to open file: " + graphFileName + " / " + contigFileName);
   return true;
 }
 
@@ -1402,6 +1480,92 @@ uint64_t mgh_graph_unitig_edges(const mgh_graph* g, mgh_unitig_edge* edges, uint
   }
   if (n_reads_total) *n_reads_total = r;
   return k;
+}
+
+namespace {
+void put_err(const std::string& e, char* err, uint64_t err_cap) {
+  if (!err || !err_cap) return;
+  const size_t n = std::min<size_t>(e.size(), err_cap - 1);
+  std::memcpy(err, e.data(), n);
+  err[n] = 0;
+}
+}  // namespace
+
+uint64_t mgh_graph_contig_edges(const mgh_graph* g, int all, mg_contig_edge* edges, uint64_t edge_cap,
+                                uint32_t* reads, uint16_t* offs, uint8_t* ors, uint64_t list_cap, uint64_t* n_list) {
+  if (n_list) *n_list = 0;
+  if (!g || !g->u) return 0;
+  try {
+    mg::ContigLists c;
+    mg::contig_edges(*g->u, all != 0, &c);
+    const uint64_t ne = std::min<uint64_t>(edge_cap, c.edges.size()), nl = std::min<uint64_t>(list_cap, c.reads.size());
+    if (edges) std::copy(c.edges.begin(), c.edges.begin() + ne, edges);
+    if (reads) std::copy(c.reads.begin(), c.reads.begin() + nl, reads);
+    if (offs) std::copy(c.offs.begin(), c.offs.begin() + nl, offs);
+    if (ors) std::copy(c.ors.begin(), c.ors.begin() + nl, ors);
+    if (n_list) *n_list = c.reads.size();
+    return c.edges.size();
+  } catch (const std::exception&) {
+    return 0;
+  }
+}
+
+int mgh_contigs_build(const uint64_t* words, const uint16_t* lens, uint64_t n_reads, uint32_t words_per_read,
+                      const mg_contig_edge* edges, uint64_t n_edges, const uint32_t* reads, const uint16_t* offs,
+                      const uint8_t* ors, uint64_t n_list, uint64_t* start, char* out, uint64_t cap, uint64_t* total,
+                      char* err, uint64_t err_cap) {
+  if (total) *total = 0;
+  put_err("", err, err_cap);
+  try {
+    std::vector<uint64_t> st;
+    std::string bases, e;
+    // sizes first; the bases only when they fit
+    int rc = mg::contigs_build(words, lens, n_reads, words_per_read, edges, n_edges, reads, offs, ors, n_list, &st,
+                               nullptr, &e, false);
+    if (rc == 0 && out && cap >= st[n_edges])
+      rc = mg::contigs_build(words, lens, n_reads, words_per_read, edges, n_edges, reads, offs, ors, n_list, &st,
+                             &bases, &e, true);
+    if (rc) {
+      put_err(e, err, err_cap);
+      return rc;
+    }
+    if (start) std::copy(st.begin(), st.end(), start);
+    if (total) *total = st[n_edges];
+    if (!bases.empty()) std::memcpy(out, bases.data(), bases.size());
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_graph_print(const mgh_graph* g, const uint64_t* words, const uint16_t* lens, uint64_t n_reads,
+                    uint32_t words_per_read, const uint64_t* start, const char* strings, const char* gdl_path,
+                    const char* fasta_path, char* err, uint64_t err_cap) {
+  put_err("", err, err_cap);
+  if (!g || !g->u || !gdl_path || !fasta_path) return -1;
+  try {
+    mg::ContigLists c;
+    mg::contig_edges(*g->u, false, &c);
+    std::vector<uint64_t> st;
+    std::string bases, e;
+    if (!start) {
+      const int rc = mg::contigs_build(words, lens, n_reads, words_per_read, c.edges.data(), c.edges.size(),
+                                       c.reads.data(), c.offs.data(), c.ors.data(), c.reads.size(), &st, &bases, &e);
+      if (rc) {
+        put_err(e, err, err_cap);
+        return rc;
+      }
+      start = st.data();
+      strings = bases.data();
+    } else {
+      for (size_t k = 0; k < c.edges.size(); ++k)
+        if (start[k + 1] < start[k]) return -1;
+      if (!strings && start[c.edges.size()] != start[0]) return -1;
+    }
+    return mg::print_graph(*g->u, c, start, strings, gdl_path, fasta_path);
+  } catch (const std::exception&) {
+    return -1;
+  }
 }
 
 namespace {

@@ -20,6 +20,12 @@
 //                OverlapGraph.h:79) as "#M read mate orient dataset" lines, reads
 //                in ID order, entries in list order, to <prefix>.mates (with -s:
 //                <prefix>.resumed.mates);
+//   -contigs     main.cpp:55's printGraph after the .unitig (also after -s):
+//                <prefix>graph1.gdl and <prefix>contigs1.fasta (the reference's
+//                names, no separator), the contig strings built on the device
+//                (MG_DEVICE_CONTIGS=0 or no device: by the host mirror), and
+//                getStringInEdge of every edge of every list in list order as
+//                "src dst orient offset nreads string" lines to <prefix>.estrings;
 //   -xchg <K>    the exchange mode over RCCL: one
 //                process per GPU (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR /
 //                MASTER_PORT as torchrun --no-python sets them; none set = one
@@ -238,9 +244,28 @@ static void save_mates(Dataset* ds, const std::string& path) {
   std::fclose(f);
 }
 
+// main.cpp:55's printGraph, and every edge's string through the drop-in's getStringInEdge
+static void save_contigs(OverlapGraph* g, Dataset* ds, const std::string& prefix) {
+  g->printGraph(prefix + "graph1.gdl", prefix + "contigs1.fasta");
+  const std::string path = prefix + ".estrings";
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) throw std::runtime_error("Unable to open file: " + path);
+  for (UINT64 u = 1; u <= ds->getNumberOfUniqueReads(); ++u) {
+    const std::vector<Edge*>* list = g->getEdges(u);
+    for (size_t j = 0; list && j < list->size(); ++j) {
+      Edge* e = list->at(j);
+      std::fprintf(f, "%llu %llu %d %llu %llu %s\n", (unsigned long long)e->getSourceRead()->getReadNumber(),
+                   (unsigned long long)e->getDestinationRead()->getReadNumber(), (int)e->getOrientation(),
+                   (unsigned long long)e->getOverlapOffset(), (unsigned long long)e->getListOfReads()->size(),
+                   g->getStringInEdge(e).c_str());
+    }
+  }
+  std::fclose(f);
+}
+
 static void usage() {
   std::fprintf(stderr,
-               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-nocontract | -raw | -s | -xchg K "
+               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-contigs] [-nocontract | -raw | -s | -xchg K "
                "[-xchg-sim P] [-xchg-caps F]]\n");
 }
 
@@ -249,7 +274,7 @@ int main(int argc, char** argv) {
   std::string prefix;
   unsigned long long l = 0;
   int k = 0, dev = 0;
-  bool raw = false, nocontract = false, resume = false, mates = false;
+  bool raw = false, nocontract = false, resume = false, mates = false, contigs = false;
   int xchg_steps = -1, xchg_sim = 0;
   double xchg_caps = 1.0;
   for (int i = 1; i < argc; ++i) {
@@ -273,6 +298,8 @@ int main(int argc, char** argv) {
       resume = true;
     } else if (a == "-mates") {
       mates = true;
+    } else if (a == "-contigs") {
+      contigs = true;
     } else if (a == "-xchg" && i + 1 < argc) {
       xchg_steps = std::max(0, std::atoi(argv[++i]));
     } else if (a == "-xchg-sim" && i + 1 < argc) {
@@ -312,6 +339,7 @@ int main(int argc, char** argv) {
       g->saveGraphToFile(prefix + ".resumed.unitig");
       g->saveGraphLists(prefix + ".resumed.graph");
       if (mates) save_mates(ds, prefix + ".resumed.mates");
+      if (contigs) save_contigs(g, ds, prefix);
       std::printf("{\"unique_reads\": %llu, \"nodes\": %llu, \"directed_edges\": %llu}\n",
                   (unsigned long long)ds->getNumberOfUniqueReads(), (unsigned long long)g->getNumberOfNodes(),
                   (unsigned long long)g->getNumberOfEdges());
@@ -331,6 +359,7 @@ int main(int argc, char** argv) {
     } else {
       g->sortEdges();  // main.cpp:49-50
       g->saveGraphToFile(prefix + ".unitig");
+      if (contigs) save_contigs(g, ds, prefix);
     }
     const mg_timings& t = g->timings();
     std::printf(

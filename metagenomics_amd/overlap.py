@@ -28,6 +28,10 @@ DISC_DTYPE = np.dtype([("dst", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("o"
 COMP_DTYPE = np.dtype([("root", "<u4"), ("n_reads", "<u4"), ("n_disc", "<u4"), ("n_self", "<u4")])
 # one entry of a read's mate list (mg_mate, include/mg_overlap.h): 8 bytes
 MATE_DTYPE = np.dtype([("id", "<u4"), ("orient", "u1"), ("dataset", "u1"), ("pad", "<u2")])
+# one edge whose string is spelled (mg_contig_edge, include/mg_overlap.h): 40 bytes
+CONTIG_EDGE_DTYPE = np.dtype({"names": ["src", "dst", "offset", "first", "n", "tail", "orient"],
+                              "formats": ["<u4", "<u4", "<u8", "<u8", "<u4", "<u4", "u1"],
+                              "offsets": [0, 4, 8, 16, 24, 28, 32], "itemsize": 40})
 
 
 class MgError(RuntimeError):
@@ -152,6 +156,11 @@ def lib() -> C.CDLL:
         "mgh_graph_save_unitig": (i32, [vp, C.c_char_p]),
         "mgh_graph_save_lists": (i32, [vp, C.c_char_p]),
         "mgh_graph_unitig_edges": (u64, [vp, vp, u64, vp, vp, vp, vp, u64, P(u64)]),
+        "mg_build_contigs": (i32, [vp, vp, u64, vp, vp, vp, u64, P(u64), P(C.c_float)]),
+        "mg_copy_contigs": (i32, [vp, vp, vp, u64, P(u64)]),
+        "mgh_graph_contig_edges": (u64, [vp, i32, vp, u64, vp, vp, vp, u64, P(u64)]),
+        "mgh_contigs_build": (i32, [vp, vp, u64, u32, vp, u64, vp, vp, vp, u64, vp, vp, u64, P(u64), C.c_char_p, u64]),
+        "mgh_graph_print": (i32, [vp, vp, vp, u64, u32, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -525,6 +534,24 @@ class OverlapEngine:
         self.build_mate_pairs(text, offsets, ppd, min_overlap, use_super)
         return self.mate_lists()
 
+    # --- contig strings (getStringInEdge of many edges at once)
+    def build_contigs(self, edges: np.ndarray, reads: np.ndarray, offs: np.ndarray, ors: np.ndarray):
+        """mg_build_contigs + mg_copy_contigs: the strings of `edges`
+        (CONTIG_EDGE_DTYPE; UnitigGraph.contig_edges gives them) over the resident
+        reads.  Returns (start uint64[n_edges + 1], bytes): the string of edge k
+        is bytes[start[k]:start[k + 1]].  contigs_ms keeps the device time of the
+        kernels.  An invalid piece raises MgError naming the edge (-2)."""
+        edges, reads, offs, ors = _contig_args(edges, reads, offs, ors)
+        total, ms = C.c_uint64(), C.c_float()
+        self._check(lib().mg_build_contigs(self._h, _ptr(edges), edges.shape[0], _ptr(reads), _ptr(offs), _ptr(ors),
+                                           reads.shape[0], C.byref(total), C.byref(ms)), "build_contigs")
+        self.contigs_ms = float(ms.value)
+        start = np.zeros(edges.shape[0] + 1, dtype=np.uint64)
+        out = np.zeros(max(int(total.value), 1), dtype=np.uint8)
+        got = C.c_uint64()
+        self._check(lib().mg_copy_contigs(self._h, _ptr(start), _ptr(out), total.value, C.byref(got)), "copy_contigs")
+        return start, out[: got.value].tobytes()
+
     # --- connected components of the lists, labelled on the device
     def build_components(self) -> int:
         """mg_build_components: label every read with the smallest read ID its
@@ -756,6 +783,34 @@ def replay_discoveries(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, mi
         L.mgh_graph_free(g)
 
 
+def _contig_args(edges, reads, offs, ors):
+    return (np.ascontiguousarray(edges, dtype=CONTIG_EDGE_DTYPE), np.ascontiguousarray(reads, dtype=np.uint32),
+            np.ascontiguousarray(offs, dtype=np.uint16), np.ascontiguousarray(ors, dtype=np.uint8))
+
+
+def host_contigs(words: np.ndarray, lens: np.ndarray, edges: np.ndarray, reads: np.ndarray, offs: np.ndarray,
+                 ors: np.ndarray):
+    """mg::contigs_build (mgh_contigs_build): the host mirror of
+    OverlapEngine.build_contigs on packed reads in ID order, on the CPU.
+    Returns (start, bytes); an invalid piece raises MgError naming the edge."""
+    words = np.ascontiguousarray(words, dtype=np.uint64)
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    edges, reads, offs, ors = _contig_args(edges, reads, offs, ors)
+    wpr = words.shape[1] if words.ndim == 2 else 1
+    start = np.zeros(edges.shape[0] + 1, dtype=np.uint64)
+    total = C.c_uint64()
+    err = C.create_string_buffer(512)
+    args = (_ptr(words), _ptr(lens), lens.shape[0], wpr, _ptr(edges), edges.shape[0], _ptr(reads), _ptr(offs),
+            _ptr(ors), reads.shape[0])
+    rc = lib().mgh_contigs_build(*args, _ptr(start), None, 0, C.byref(total), err, 512)
+    out = np.zeros(max(int(total.value), 1), dtype=np.uint8)
+    if rc == 0:
+        rc = lib().mgh_contigs_build(*args, _ptr(start), _ptr(out), total.value, C.byref(total), err, 512)
+    if rc:
+        raise MgError(f"host_contigs: {err.value.decode() or 'bad arguments'} ({rc})")
+    return start, out[: total.value].tobytes()
+
+
 def read_pairs(files: Sequence[str] | None = None, data: bytes | None = None):
     """The mates of every pair as storeMatePairInformation's loop reads them
     (mgh_read_pairs; `data`: one file's bytes).  Returns (text bytes, offsets
@@ -950,6 +1005,42 @@ class UnitigGraph:
         L.mgh_graph_unitig_edges(self._g, _ptr(e), n, _ptr(st), _ptr(reads), _ptr(offs), _ptr(ors), nr.value,
                                  C.byref(nr))
         return e, st, reads, offs, ors
+
+    def contig_edges(self, all_edges: bool = False):
+        """(edges[CONTIG_EDGE_DTYPE], reads, offs, ors): printGraph's contigs in
+        its selection order (OverlapGraph.cpp:460), or with all_edges every edge
+        of every list in list order, as build_contigs / host_contigs take them."""
+        L = self._L
+        nl = C.c_uint64()
+        n = int(L.mgh_graph_contig_edges(self._g, int(all_edges), None, 0, None, None, None, 0, C.byref(nl)))
+        e = np.zeros(n, dtype=CONTIG_EDGE_DTYPE)
+        reads = np.zeros(nl.value, dtype=np.uint32)
+        offs = np.zeros(nl.value, dtype=np.uint16)
+        ors = np.zeros(nl.value, dtype=np.uint8)
+        L.mgh_graph_contig_edges(self._g, int(all_edges), _ptr(e), n, _ptr(reads), _ptr(offs), _ptr(ors), nl.value,
+                                 C.byref(nl))
+        return e, reads, offs, ors
+
+    def print_graph(self, ds, gdl: str, fasta: str, engine=None):
+        """printGraph (OverlapGraph.cpp:428-520): the .gdl file and the contigs as
+        FASTA.  ds = the Dataset (or a (words, lens) pair in ID order).  With an
+        engine that holds these reads the strings are built on the device
+        (OverlapEngine.build_contigs), otherwise by the host mirror."""
+        words, lens = ds.packed() if hasattr(ds, "packed") else ds
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint16)
+        wpr = words.shape[1] if words.ndim == 2 else 1
+        start = strings = None
+        if engine is not None:
+            start, strings = engine.build_contigs(*self.contig_edges())
+            strings = np.frombuffer(strings + b"\0", dtype=np.uint8)
+        err = C.create_string_buffer(512)
+        rc = self._L.mgh_graph_print(self._g, _ptr(words), _ptr(lens), lens.shape[0], wpr,
+                                     None if start is None else _ptr(start),
+                                     None if strings is None else _ptr(strings), os.fsencode(gdl), os.fsencode(fasta),
+                                     err, 512)
+        if rc:
+            raise MgError(f"print_graph: {err.value.decode() or 'cannot write ' + gdl + ' / ' + fasta} ({rc})")
 
     def close(self):
         if self._g:
