@@ -137,7 +137,8 @@ class Edge {
   std::vector<UINT8>* getListOfOrientations() { return &listOfOrientations; }
   bool transitiveRemovalFlag = false;
   UINT16 flow = 0;  // Edge.h:42 (0 until flow is computed)
-  UINT64 coverageDepth = 0;  // Edge.h:43 (0 until flow is computed)
+  UINT64 coverageDepth = 0;  // Edge.h:43 (0 until getBaseByBaseCoverage / calculateCoverageOfAllEdges)
+  UINT64 SD = 0;             // Edge.h:44: standard deviation of the per-base coverage
 
  private:
   friend class OverlapGraph;
@@ -311,6 +312,29 @@ class OverlapGraph {
   bool printGraph(std::string graphFileName, std::string contigFileName);
   // Until this is called the environment variable MG_DEVICE_CONTIGS decides (0 = host mirror).
   static void setDeviceContigs(bool on);
+  // calculateMeanAndSdOfInsertSize (:1124-1211): mean and SD of the insert sizes
+  // of every paired-end dataset over the current edges; true at once when there
+  // is no paired-end file.  The placements of every read (updateReadLocations of
+  // every edge) and the sums are built on the device (mg_build_placements,
+  // mg_insert_sizes) in the hash table's context while a build holds one, else
+  // in a context of its own; without a HIP device, or with device placements
+  // off, by the host mirrors (mg::placements_build, mg::insert_sizes).  The same
+  // values either way.  The reference's cout lines are not printed here
+  // (mg_overlap -insert prints them).
+  bool calculateMeanAndSdOfInsertSize();
+  UINT64 getMean(UINT64 datasetNumber) { return meanOfInsertSizes.at(datasetNumber); }  // OverlapGraph.h:62
+  UINT64 getSD(UINT64 datasetNumber) { return sdOfInsertSizes.at(datasetNumber); }      // OverlapGraph.h:63
+  // not in the reference: the number of insert sizes behind getMean(d) ("Reads on same edge: ")
+  UINT64 getNumberOfInsertSizes(UINT64 datasetNumber) { return numberOfInsertSizes.at(datasetNumber); }
+  // getBaseByBaseCoverage (:2722-2792): sets edge->coverageDepth and edge->SD,
+  // by the host mirror (mg::edge_coverage); where the reference's at() would
+  // throw this throws std::out_of_range naming the entry
+  void getBaseByBaseCoverage(Edge* edge);
+  // not in the reference: getBaseByBaseCoverage of every edge of the graph in
+  // one device call (mg_edge_coverage; contexts and fall-back as above)
+  void calculateCoverageOfAllEdges();
+  // Until this is called the environment variable MG_DEVICE_PLACES decides (0 = host mirrors).
+  static void setDevicePlacements(bool on);
   const mg_timings& timings() const { return lastTimings; }
 
  private:
@@ -318,6 +342,7 @@ class OverlapGraph {
   HashTable* hashTable = nullptr;
   std::vector<std::vector<Edge*>*>* graph = nullptr;
   UINT64 numberOfNodes = 0, numberOfEdges = 0;
+  std::vector<UINT64> meanOfInsertSizes, sdOfInsertSizes, numberOfInsertSizes;  // OverlapGraph.h:38-39
   bool containedDone = false;
   mg_timings lastTimings{};
   mg::UnitigGraph* unitig = nullptr;  // the list state the contraction steps work on

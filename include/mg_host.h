@@ -248,6 +248,44 @@ int mgh_graph_print(const mgh_graph* g, const uint64_t* words, const uint16_t* l
                     uint32_t words_per_read, const uint64_t* start, const char* strings, const char* gdl_path,
                     const char* fasta_path, char* err, uint64_t err_cap);
 
+/* --- read placements, insert sizes, edge coverage (OverlapGraph.cpp:1048-1071,
+ * 1124-1211, 2722-2792): the host mirrors of mg_build_placements +
+ * mg_copy_placements, mg_insert_sizes and mg_edge_coverage (mg::placements_build,
+ * mg::insert_sizes, mg::edge_coverage): linear restatements of the reference's
+ * loops over the same arrays, with the same -2 errors.  err (err_cap bytes,
+ * NUL-terminated, optional) gets the message. */
+/* start: n_reads + 2 entries; out: cap records, written only when cap >= the
+ * total; fwd_count: n_reads + 2 entries (forward placements per read ID).  Any
+ * of them may be NULL.  0 = ok; -1 = bad arguments; -2 = a read ID outside
+ * 1..n_reads. */
+int mgh_placements_build(uint64_t n_reads, const mg_contig_edge* edges, uint64_t n_edges, const uint32_t* reads,
+                         const uint16_t* offs, const uint8_t* ors, uint64_t n_list, uint64_t* start, mg_place* out,
+                         uint64_t cap, uint32_t* fwd_count, uint64_t* n_places, char* err, uint64_t err_cap);
+/* place_start / places: a placement CSR (n_reads + 2 starts); mate_start /
+ * mates: a mate CSR in mg_copy_mate_pairs' layout; sums: 3 * n_datasets. */
+int mgh_insert_sizes(uint64_t n_reads, const uint64_t* place_start, const mg_place* places,
+                     const uint64_t* mate_start, const mg_mate* mates, uint32_t n_datasets, uint64_t max_distance,
+                     uint64_t* sums, char* err, uint64_t err_cap);
+/* lens[id - 1], freq[id - 1]; out: 3 * n_edges (count, sum, sum of squares over
+ * the non-zero counters of each edge).  The forward-placement counts are those
+ * of the same edges.  64-bit counters: no limit on an edge's frequency sum. */
+int mgh_edge_coverage(const uint16_t* lens, uint64_t n_reads, const mg_contig_edge* edges, uint64_t n_edges,
+                      const uint32_t* reads, const uint16_t* offs, const uint8_t* ors, uint64_t n_list,
+                      const uint32_t* freq, uint64_t* out, char* err, uint64_t err_cap);
+/* mean and sd from count, sum and sum of squares as the reference computes
+ * them (:1196-1201, :2776-2786): mean = sum / count, variance = sumsq - 2 mean
+ * sum + count mean^2 (mod 2^64), sd = (uint64)sqrt((double)(variance / count));
+ * count == 0 gives 0, 0. */
+void mgh_mean_sd(uint64_t count, uint64_t sum, uint64_t sumsq, uint64_t* mean, uint64_t* sd);
+/* The read locations a contracted or re-read handle tracked (updateReadLocations
+ * / removeReadLocations through the contraction) as placements: edge = the
+ * edge's index in mgh_graph_contig_edges(all = 1); each read's records sorted by
+ * (edge, distance, flags).  *n_reads (optional) = the reads the handle tracks (0
+ * for a handle that tracked no locations); start: *n_reads + 2 entries; out:
+ * cap records; either may be NULL.  Returns the number of records. */
+uint64_t mgh_graph_read_locations(const mgh_graph* g, uint64_t* n_reads, uint64_t* start, mg_place* out,
+                                  uint64_t cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -311,6 +311,84 @@ int mg_build_contigs(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edges,
  * mg_build_contigs succeeded for the current reads. */
 int mg_copy_contigs(mg_ctx* ctx, uint64_t* start, char* out, uint64_t cap, uint64_t* n_copied);
 
+/* --- read placements, insert sizes, edge coverage ---------------------------
+ * (OverlapGraph::updateReadLocations :1048-1071, calculateMeanAndSdOfInsertSize
+ * :1124-1211, getBaseByBaseCoverage :2722-2792)
+ * One placement of a read: list entry i of edge k places reads[first + i] on
+ * edge k at distance D(k, i) = offs[first] + ... + offs[first + i], forward iff
+ * ors[first + i] == 1.  A read's forward placements are its
+ * getListOfEdgesForward / getLocationOnEdgeForward, the others the ...Reverse
+ * pair.  16 bytes. */
+typedef struct mg_place {
+  uint32_t edge;     /* index into the edges given to mg_build_placements */
+  uint32_t flags;    /* bit 0 = forward */
+  uint64_t distance; /* D(k, i) */
+} mg_place;
+/* updateReadLocations (:1048-1071) of every edge at once.  `edges` and the
+ * shared lists are what mg_build_contigs takes, every directed edge once
+ * (mgh_graph_contig_edges(all = 1)); src, dst, offset, tail and orient are not
+ * read here (mg_edge_coverage reads src, dst and offset).  Builds one CSR of
+ * mg_place over the reads, each read's records in ascending (edge index, list
+ * position) -- the reference's order inside a read's lists depends on the
+ * contraction history, so only the set is promised to equal its lists -- and
+ * each read's forward-placement count.  One 64-bit device-wide inclusive scan
+ * of the offsets with each edge's base subtracted gives the distances; one
+ * stable radix sort of the entries by read ID gives the CSR in the promised
+ * order.  Needs only a context that holds the reads (any upload or ingest,
+ * either slot layout, any width, long reads included); a sharded or
+ * exchange-mode context refuses.  *n_places = total records (the edges' n
+ * together, < 2^31); *device_ms (optional) = HIP-event time of the kernels (no
+ * transfers).  Errors: -1 (bad arguments, a list range outside n_list, a HIP
+ * error); -2 a read ID outside 1..n_reads: mg_last_error names the first such
+ * edge and entry.  The CSR stays on the device until the next upload or ingest. */
+int mg_build_placements(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edges, const uint32_t* reads,
+                        const uint16_t* offs, const uint8_t* ors, uint64_t n_list, uint64_t* n_places,
+                        float* device_ms);
+/* start: n_reads + 2 entries (as mg_copy_mate_pairs), the placements of read A =
+ * out[start[A] .. start[A+1]); out: cap records.  Either may be NULL.  Fails
+ * unless mg_build_placements succeeded for the current reads. */
+int mg_copy_placements(mg_ctx* ctx, uint64_t* start, mg_place* out, uint64_t cap, uint64_t* n_copied);
+/* The sums behind calculateMeanAndSdOfInsertSize (:1140-1179).  For every read
+ * A, every entry (B, orient, dataset = d) of A's mate list, every placement p
+ * of A and q of B (either strand each) with p.edge == q.edge, p.distance >
+ * q.distance and x = p.distance - q.distance < max_distance (the reference's
+ * 1000): sums[3 d] += 1, sums[3 d + 1] += x, sums[3 d + 2] += x * x (64-bit,
+ * wrapping); every matching (p, q) combination counts.  The host finishes:
+ * mean = sum / count, variance = sumsq - 2 mean sum + count mean^2 (mod 2^64),
+ * sd = (uint64)sqrt((double)(variance / count)); count == 0 gives 0, 0.
+ * mate_start == NULL: the resident lists of mg_build_mate_pairs; otherwise a
+ * CSR in mg_copy_mate_pairs' layout (mate_start: n_reads + 2 non-decreasing
+ * entries, mate_start[0] = 0; mates: mate_start[n_reads + 1] records).  One
+ * thread per mate entry; the integer sums are reduced across the wavefront
+ * and leave it as one 64-bit atomic per counter, so the result does not depend
+ * on the order.  sums: 3 * n_datasets entries.  Errors: -1 (bad arguments, no
+ * placements, no resident mate lists); -2 a mate entry whose dataset >=
+ * n_datasets or whose owner or mate ID lies outside 1..n_reads:
+ * mg_last_error names the first such entry. */
+int mg_insert_sizes(mg_ctx* ctx, const uint64_t* mate_start, const mg_mate* mates, uint32_t n_datasets,
+                    uint64_t max_distance, uint64_t* sums, float* device_ms);
+/* getBaseByBaseCoverage (:2722-2792) of every edge of the last
+ * mg_build_placements.  Edge k: L = offset + len(dst), counters c[0 .. L];
+ * every list entry adds freq[read - 1] to c[D, D + len(read)); every entry
+ * whose read has more than one forward placement over all edges zeroes its
+ * interval (the reference tests the forward list only); then c[0, len(src)) and
+ * the last len(dst) counters are zeroed; out[3 k .. 3 k + 2] = count, sum and
+ * sum of squares (64-bit, wrapping) over the non-zero counters.  The host
+ * finishes mean and sd as for the insert sizes.  freq: n_reads entries, or NULL
+ * = the frequencies the device ingest left (an error when the reads were
+ * uploaded).  Per base one 64-bit delta word (zeroing entries in the high half,
+ * frequencies in the low half) takes integer atomics at interval starts and
+ * ends, one scan turns the deltas into counters and one pass reduces them per
+ * edge, so interval ends need not be monotone.  Edges are taken in chunks of at
+ * most "cov_budget" counters (mg_set_option; an edge above it is a chunk of its
+ * own).  Errors: -1 (bad arguments, no placements, no frequencies, an edge
+ * whose offset is >= 2^40, an edge whose list frequencies sum to >= 2^32: the
+ * frequency half of a delta word is 32 bits wide); -2 an invalid edge, where
+ * the reference's at() would throw: src or dst outside 1..n_reads, D + len(read)
+ * > L + 1, or len(src) > L + 1: mg_last_error names the first such edge (and
+ * entry) and no result is written. */
+int mg_edge_coverage(mg_ctx* ctx, const uint32_t* freq, uint64_t* out, float* device_ms);
+
 /* --- sharding (multi-GPU, one process per GPU) ---------------------------- */
 /* Restrict this context to index buckets owned by `rank` of `nranks`
  * (bucket-range sharding) and/or to the source reads with
@@ -525,6 +603,8 @@ int mg_get_counters(const mg_ctx* ctx, mg_counters* c);
  *  "disc_block_cap" tests: records per read the workgroup sort of mg_build_discoveries
  *                   takes (0 = default 2,048; at least 64, where the wavefront path
  *                   ends); longer lists take the segmented radix sort;
+ *  "cov_budget"     tests: per-base counters one chunk of mg_edge_coverage holds
+ *                   (0 = default 2^25); an edge above it is a chunk of its own;
  *  "phase_limit", "max_blocks"
  *                   diagnostics: stop the probe after a phase / cap its grid. */
 int mg_set_option(mg_ctx* ctx, const char* name, int64_t value);

@@ -2,7 +2,8 @@
 // shared by the kernel translation units (mg_kernels.hip: index + discovery +
 // exchange; mg_dataset.hip: Dataset ingest on the device; mg_disc.hip: the
 // per-read discovery lists D(A); mg_comp.hip: their components; mg_mates.hip:
-// read lookup and the per-read mate lists; mg_contigs.hip: the strings of edges).
+// read lookup and the per-read mate lists; mg_contigs.hip: the strings of edges;
+// mg_places.hip: read placements, insert sizes and edge coverage).
 #ifndef MG_CTX_HPP_
 #define MG_CTX_HPP_
 #include <hip/hip_runtime.h>
@@ -406,6 +407,36 @@ struct mg_ctx {
   unsigned long long* d_ctg_ctl = nullptr;  // [0] = first invalid piece
   size_t ctg_ctl_cap = 0;
   hipEvent_t ctg_ev[2] = {};
+  // read placements (mg_places.hip, mg_build_placements): one CSR of mg_place
+  // records over the reads, each read's forward-placement count, and what
+  // mg_edge_coverage reads again: the edges and, per list entry of every edge
+  // ("entry space", edge k at pl_ebase[k]), its read, edge and distance.
+  // places_ready until new reads arrive (reset_derived)
+  bool places_ready = false;
+  uint64_t n_places = 0;
+  std::vector<mg_contig_edge> pl_edges;  // the edges of the last build (messages, chunking)
+  std::vector<uint64_t> pl_ebase;        // per edge (+ 1): its first entry
+  uint64_t* d_pl_start = nullptr;  // start[A] (n + 2)
+  size_t pl_start_cap = 0;
+  mg_place* d_places = nullptr;
+  size_t places_cap = 0;
+  uint32_t* d_pl_fwd = nullptr;  // forward placements of read A (n + 2)
+  size_t pl_fwd_cap = 0;
+  mg_contig_edge* d_pl_edges = nullptr;
+  size_t pl_edges_cap = 0;
+  uint64_t* d_pl_ebase = nullptr;
+  size_t pl_ebase_cap = 0;
+  uint32_t* d_pl_eread = nullptr;
+  size_t pl_eread_cap = 0;
+  uint32_t* d_pl_eedge = nullptr;
+  size_t pl_eedge_cap = 0;
+  uint64_t* d_pl_edist = nullptr;
+  size_t pl_edist_cap = 0;
+  // option "cov_budget" (tests): per-base counters one chunk of mg_edge_coverage holds (0 = 2^25)
+  uint64_t cov_budget = 0;
+  // d_freq belongs to the resident reads (set by the device ingest, cleared by an upload)
+  bool freq_ready = false;
+  hipEvent_t pl_ev[2] = {};
 };
 
 #define MG_TRY(expr)                                                                  \
@@ -506,6 +537,7 @@ inline void reset_derived(mg_ctx* ctx) {
   ctx->comp_ready = false;
   ctx->mates_ready = false;
   ctx->contigs_ready = false;
+  ctx->places_ready = false;
 }
 
 // mg_dataset.hip: the ingest's per-record stage alone (k_ingest / k_ingest_long
@@ -520,6 +552,8 @@ int ingest_records(mg_ctx* ctx, const char* d_ascii, const uint64_t* d_off, uint
 void mates_release(mg_ctx* ctx);
 // mg_contigs.hip: frees the contig buffers (mg_destroy)
 void contigs_release(mg_ctx* ctx);
+// mg_places.hip: frees the placement buffers (mg_destroy)
+void places_release(mg_ctx* ctx);
 
 // mg_disc.hip: frees the discovery-list buffers (mg_destroy)
 void disc_release(mg_ctx* ctx);

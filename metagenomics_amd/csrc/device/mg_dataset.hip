@@ -372,6 +372,7 @@ struct Ingest {
     ctx->maxlen = ngood ? lrh[1] : 0;
     if (apply_layout(ctx)) return -1;
     reset_derived(ctx);
+    ctx->freq_ready = true;
     *n_unique = nu;
     return 0;
   }

@@ -4003,6 +4003,7 @@ void mg_destroy(mg_ctx* ctx) {
   comp_release(ctx);
   mates_release(ctx);
   contigs_release(ctx);
+  places_release(ctx);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);
@@ -4030,6 +4031,7 @@ static int finish_upload(mg_ctx* ctx, const uint16_t* lens_host) {
   ctx->maxlen = mx;
   if (apply_layout(ctx)) return -1;
   reset_derived(ctx);
+  ctx->freq_ready = false;  // (d_freq, if any, belongs to an earlier ingest)
   return 0;
 }
 
@@ -4225,6 +4227,10 @@ int mg_set_option(mg_ctx* ctx, const char* name, int64_t value) {
   }
   if (!strcmp(name, "disc_block_cap")) {  // tests: records the discovery lists' workgroup sort takes (0 = default)
     ctx->disc_block_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+    return 0;
+  }
+  if (!strcmp(name, "cov_budget")) {  // tests: per-base counters per chunk of mg_edge_coverage (0 = default)
+    ctx->cov_budget = (uint64_t)std::max<int64_t>(0, value);
     return 0;
   }
   if (!strcmp(name, "run_cap")) {  // tests: initial run records per scan region (0 = sized from the reads)

@@ -20,6 +20,7 @@
 #include "mg_contigs.hpp"
 #include "mg_mates.hpp"
 #include "mg_parse.hpp"
+#include "mg_places.hpp"
 #include "mg_unitig.hpp"
 #include "mg_graph.hpp"
 #include "mg_host.h"
@@ -786,6 +787,166 @@ bool OverlapGraph::printGraph(std::string graphFileName, std::string contigFileN
   if (mg::print_graph(*unitig, c, start.data(), bases.data(), graphFileName.c_str(), contigFileName.c_str()))
     throw mg::Error("Unable to open file: " + graphFileName + " / " + contigFileName);
   return true;
+}
+
+namespace {
+// g_device_places: OverlapGraph::setDevicePlacements; -1 = not called, the
+// environment variable MG_DEVICE_PLACES decides (unset: device)
+int g_device_places = -1;
+
+bool use_device_places(UINT64 n_reads) {
+  const char* v = std::getenv("MG_DEVICE_PLACES");
+  const bool on = g_device_places < 0 ? (v && *v ? std::atoi(v) != 0 : true) : g_device_places != 0;
+  return on && n_reads && mg_device_count() > 0;
+}
+
+// the hash table's context while a build holds one for these reads, else a
+// context of its own with the Dataset's packed reads (freed on destruction)
+struct PlaceCtx {
+  mg_ctx* ctx = nullptr;
+  bool own = false;
+  PlaceCtx(HashTable* ht, Dataset* ds, const char* who) {
+    const UINT64 N = ds->getNumberOfUniqueReads();
+    ctx = ht ? ht->context() : nullptr;
+    if (ctx && mg_num_reads(ctx) != N) ctx = nullptr;
+    if (ctx) return;
+    if (mg_create(&ctx, mg::g_default_device)) throw mg::Error(std::string(who) + ": cannot create a device context");
+    own = true;
+    if (mg_upload_reads_packed(ctx, ds->packedWords(), ds->packedLengths(), N, ds->wordsPerRead())) {
+      const std::string why = mg_last_error(ctx);
+      mg_destroy(ctx);
+      throw mg::Error(std::string(who) + ": upload: " + why);
+    }
+  }
+  ~PlaceCtx() {
+    if (own) mg_destroy(ctx);
+  }
+  PlaceCtx(const PlaceCtx&) = delete;
+  PlaceCtx& operator=(const PlaceCtx&) = delete;
+};
+}  // namespace
+
+void OverlapGraph::setDevicePlacements(bool on) { g_device_places = on ? 1 : 0; }
+
+bool OverlapGraph::calculateMeanAndSdOfInsertSize() {
+  if (!dataSet) throw mg::Error("calculateMeanAndSdOfInsertSize: no Dataset");
+  const uint32_t D = (uint32_t)dataSet->pairedEndDatasetFileNames.size();
+  if (D == 0) return true;  // :1127-1128
+  adoptEdgeLists();
+  if (!unitig) throw mg::Error("calculateMeanAndSdOfInsertSize: no replayed graph");
+  if (D > 256) throw mg::Error("calculateMeanAndSdOfInsertSize: more than 256 paired-end files (datasetNumber is UINT8)");
+  const UINT64 N = dataSet->getNumberOfUniqueReads();
+  mg::ContigLists c;
+  mg::contig_edges(*unitig, true, &c);
+  // the mate lists as the C-ABI takes them (empty before readMatePairsFromFile)
+  std::vector<uint64_t> mstart(N + 2, 0);
+  std::vector<mg_mate> mates(dataSet->mates.size());
+  if (dataSet->mateStart.size() == N + 2) mstart = dataSet->mateStart;
+  else mates.clear();
+  for (size_t i = 0; i < mates.size(); ++i)
+    mates[i] = mg_mate{(uint32_t)dataSet->mates[i].matePairID, dataSet->mates[i].matePairOrientation,
+                       dataSet->mates[i].datasetNumber, 0};
+  std::vector<uint64_t> sums(3 * (size_t)D, 0);
+  if (use_device_places(N)) {
+    PlaceCtx pc(hashTable, dataSet, "calculateMeanAndSdOfInsertSize");
+    uint64_t n_places = 0;
+    if (mg_build_placements(pc.ctx, c.edges.data(), c.edges.size(), c.reads.data(), c.offs.data(), c.ors.data(),
+                            c.reads.size(), &n_places, nullptr) ||
+        mg_insert_sizes(pc.ctx, mstart.data(), mates.data(), D, 1000, sums.data(), nullptr))
+      throw mg::Error(std::string("calculateMeanAndSdOfInsertSize: ") + mg_last_error(pc.ctx));
+  } else {
+    std::vector<uint64_t> pstart;
+    std::vector<mg_place> places;
+    std::vector<uint32_t> fwd;
+    std::string err;
+    if (mg::placements_build(N, c.edges.data(), c.edges.size(), c.reads.data(), c.offs.data(), c.ors.data(),
+                             c.reads.size(), &pstart, &places, &fwd, &err) ||
+        mg::insert_sizes(N, pstart.data(), places.data(), mstart.data(), mates.data(), D, 1000, sums.data(), &err))
+      throw mg::Error("calculateMeanAndSdOfInsertSize: " + err);
+  }
+  meanOfInsertSizes.assign(D, 0);
+  sdOfInsertSizes.assign(D, 0);
+  numberOfInsertSizes.assign(D, 0);
+  for (uint32_t d = 0; d < D; ++d) {
+    uint64_t mean = 0, sd = 0;
+    mg::mean_sd(sums[3 * d], sums[3 * d + 1], sums[3 * d + 2], &mean, &sd);  // :1181-1201
+    meanOfInsertSizes[d] = mean;
+    sdOfInsertSizes[d] = sd;
+    numberOfInsertSizes[d] = sums[3 * d];
+  }
+  return true;
+}
+
+void OverlapGraph::getBaseByBaseCoverage(Edge* edge) {
+  if (!edge || !dataSet) throw mg::Error("getBaseByBaseCoverage: no edge / no Dataset");
+  const UINT64 N = dataSet->getNumberOfUniqueReads();
+  mg_contig_edge c{};
+  c.src = (uint32_t)edge->getSourceRead()->getReadNumber();
+  c.dst = (uint32_t)edge->getDestinationRead()->getReadNumber();
+  c.offset = edge->getOverlapOffset();
+  c.n = (uint32_t)edge->getListOfReads()->size();
+  c.orient = edge->getOrientation();
+  const std::vector<uint32_t> reads(edge->getListOfReads()->begin(), edge->getListOfReads()->end());
+  // getListOfEdgesForward()->size() (:2748) and getFrequency() of the reads of this edge
+  std::vector<uint32_t> fwd(N + 2, 0), freq(N, 0);
+  for (uint32_t id : reads) {
+    if (id < 1 || id > N) continue;  // (the mirror reports it)
+    Read* r = dataSet->getReadFromID(id);
+    fwd[id] = r->loc ? (uint32_t)r->loc->edgesForward.size() : 0;
+    freq[id - 1] = dataSet->frequencyOf(id);
+  }
+  uint64_t out[3] = {0, 0, 0};
+  std::string err;
+  const int rc = mg::edge_coverage(dataSet->packedLengths(), N, &c, 1, reads.data(),
+                                   edge->getListOfOverlapOffsets()->data(), edge->getListOfOrientations()->data(), c.n,
+                                   fwd.data(), freq.data(), out, &err);
+  if (rc == -2) throw std::out_of_range("getBaseByBaseCoverage: " + err);
+  if (rc) throw mg::Error("getBaseByBaseCoverage: " + err);
+  uint64_t mean = 0, sd = 0;
+  mg::mean_sd(out[0], out[1], out[2], &mean, &sd);
+  edge->coverageDepth = mean;  // :2789-2790
+  edge->SD = sd;
+}
+
+void OverlapGraph::calculateCoverageOfAllEdges() {
+  if (!dataSet) throw mg::Error("calculateCoverageOfAllEdges: no Dataset");
+  adoptEdgeLists();
+  if (!unitig || !graph) throw mg::Error("calculateCoverageOfAllEdges: no replayed graph");
+  const UINT64 N = dataSet->getNumberOfUniqueReads();
+  mg::ContigLists c;
+  mg::contig_edges(*unitig, true, &c);  // u order, list order: the order of the Edge lists
+  std::vector<uint32_t> freq(N, 0);
+  for (UINT64 i = 1; i <= N; ++i) freq[i - 1] = dataSet->frequencyOf(i);
+  std::vector<uint64_t> out(3 * c.edges.size(), 0);
+  if (use_device_places(N)) {
+    PlaceCtx pc(hashTable, dataSet, "calculateCoverageOfAllEdges");
+    uint64_t n_places = 0;
+    if (mg_build_placements(pc.ctx, c.edges.data(), c.edges.size(), c.reads.data(), c.offs.data(), c.ors.data(),
+                            c.reads.size(), &n_places, nullptr) ||
+        mg_edge_coverage(pc.ctx, freq.data(), out.data(), nullptr))
+      throw mg::Error(std::string("calculateCoverageOfAllEdges: ") + mg_last_error(pc.ctx));
+  } else {
+    std::vector<uint64_t> pstart;
+    std::vector<mg_place> places;
+    std::vector<uint32_t> fwd;
+    std::string err;
+    if (mg::placements_build(N, c.edges.data(), c.edges.size(), c.reads.data(), c.offs.data(), c.ors.data(),
+                             c.reads.size(), &pstart, &places, &fwd, &err) ||
+        mg::edge_coverage(dataSet->packedLengths(), N, c.edges.data(), c.edges.size(), c.reads.data(), c.offs.data(),
+                          c.ors.data(), c.reads.size(), fwd.data(), freq.data(), out.data(), &err))
+      throw mg::Error("calculateCoverageOfAllEdges: " + err);
+  }
+  size_t k = 0;
+  for (UINT64 u = 1; u <= N && u < graph->size(); ++u)
+    for (Edge* e : *(*graph)[u]) {
+      if (k >= c.edges.size() || c.edges[k].src != u || c.edges[k].dst != e->getDestinationRead()->getReadNumber())
+        throw mg::Error("calculateCoverageOfAllEdges: the Edge lists and the list state are out of step");
+      uint64_t mean = 0, sd = 0;
+      mg::mean_sd(out[3 * k], out[3 * k + 1], out[3 * k + 2], &mean, &sd);
+      e->coverageDepth = mean;
+      e->SD = sd;
+      ++k;
+    }
 }
 
 void OverlapGraph::markContainedReads() {
@@ -1565,6 +1726,108 @@ int mgh_graph_print(const mgh_graph* g, const uint64_t* words, const uint16_t* l
     return mg::print_graph(*g->u, c, start, strings, gdl_path, fasta_path);
   } catch (const std::exception&) {
     return -1;
+  }
+}
+
+int mgh_placements_build(uint64_t n_reads, const mg_contig_edge* edges, uint64_t n_edges, const uint32_t* reads,
+                         const uint16_t* offs, const uint8_t* ors, uint64_t n_list, uint64_t* start, mg_place* out,
+                         uint64_t cap, uint32_t* fwd_count, uint64_t* n_places, char* err, uint64_t err_cap) {
+  if (n_places) *n_places = 0;
+  put_err("", err, err_cap);
+  try {
+    std::vector<uint64_t> st;
+    std::vector<mg_place> pl;
+    std::vector<uint32_t> fc;
+    std::string e;
+    const int rc = mg::placements_build(n_reads, edges, n_edges, reads, offs, ors, n_list, &st, &pl, &fc, &e);
+    if (rc) {
+      put_err(e, err, err_cap);
+      return rc;
+    }
+    if (start) std::copy(st.begin(), st.end(), start);
+    if (fwd_count) std::copy(fc.begin(), fc.end(), fwd_count);
+    if (out && cap >= pl.size()) std::copy(pl.begin(), pl.end(), out);
+    if (n_places) *n_places = pl.size();
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_insert_sizes(uint64_t n_reads, const uint64_t* place_start, const mg_place* places,
+                     const uint64_t* mate_start, const mg_mate* mates, uint32_t n_datasets, uint64_t max_distance,
+                     uint64_t* sums, char* err, uint64_t err_cap) {
+  put_err("", err, err_cap);
+  try {
+    std::string e;
+    const int rc = mg::insert_sizes(n_reads, place_start, places, mate_start, mates, n_datasets, max_distance, sums, &e);
+    if (rc) put_err(e, err, err_cap);
+    return rc;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+
+int mgh_edge_coverage(const uint16_t* lens, uint64_t n_reads, const mg_contig_edge* edges, uint64_t n_edges,
+                      const uint32_t* reads, const uint16_t* offs, const uint8_t* ors, uint64_t n_list,
+                      const uint32_t* freq, uint64_t* out, char* err, uint64_t err_cap) {
+  put_err("", err, err_cap);
+  try {
+    std::vector<uint64_t> st;
+    std::vector<mg_place> pl;
+    std::vector<uint32_t> fc;
+    std::string e;
+    int rc = mg::placements_build(n_reads, edges, n_edges, reads, offs, ors, n_list, &st, &pl, &fc, &e);
+    if (!rc) rc = mg::edge_coverage(lens, n_reads, edges, n_edges, reads, offs, ors, n_list, fc.data(), freq, out, &e);
+    if (rc) put_err(e, err, err_cap);
+    return rc;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+
+void mgh_mean_sd(uint64_t count, uint64_t sum, uint64_t sumsq, uint64_t* mean, uint64_t* sd) {
+  uint64_t m = 0, s = 0;
+  mg::mean_sd(count, sum, sumsq, &m, &s);
+  if (mean) *mean = m;
+  if (sd) *sd = s;
+}
+
+uint64_t mgh_graph_read_locations(const mgh_graph* g, uint64_t* n_reads_out, uint64_t* start, mg_place* out,
+                                  uint64_t cap) {
+  if (n_reads_out) *n_reads_out = 0;
+  if (!g || !g->u || !g->u->track || g->u->loc_fwd.empty()) return 0;
+  try {
+    const mg::UnitigGraph& u = *g->u;
+    mg::ContigLists c;
+    mg::contig_edges(u, true, &c);
+    std::vector<uint32_t> index(u.pool.size(), 0xFFFFFFFFu);  // pool entry -> index among all edges
+    for (size_t k = 0; k < c.pool.size(); ++k) index[c.pool[k]] = (uint32_t)k;
+    const uint64_t n_reads = u.loc_fwd.size() - 1;
+    if (n_reads_out) *n_reads_out = n_reads;
+    std::vector<mg_place> recs;
+    uint64_t total = 0;
+    if (start) start[0] = start[1] = 0;
+    for (uint64_t r = 1; r <= n_reads; ++r) {
+      recs.clear();
+      for (int side = 0; side < 2; ++side)
+        for (const mg::ReadLoc& l : side ? u.loc_rev[r] : u.loc_fwd[r])
+          recs.push_back(mg_place{index[l.edge], side ? 0u : 1u, l.loc});
+      std::sort(recs.begin(), recs.end(), [](const mg_place& a, const mg_place& b) {
+        if (a.edge != b.edge) return a.edge < b.edge;
+        if (a.distance != b.distance) return a.distance < b.distance;
+        return a.flags < b.flags;
+      });
+      if (start) start[r] = total;
+      for (const mg_place& p : recs) {
+        if (out && total < cap) out[total] = p;
+        ++total;
+      }
+    }
+    if (start) start[n_reads + 1] = total;
+    return total;
+  } catch (const std::exception&) {
+    return 0;
   }
 }
 

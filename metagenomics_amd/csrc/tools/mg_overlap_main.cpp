@@ -26,6 +26,15 @@
 //                (MG_DEVICE_CONTIGS=0 or no device: by the host mirror), and
 //                getStringInEdge of every edge of every list in list order as
 //                "src dst orient offset nreads string" lines to <prefix>.estrings;
+//   -insert      main.cpp:59's calculateMeanAndSdOfInsertSize after the .unitig (also
+//                after -s), for use with -pe: per dataset the reference's three
+//                stdout lines ("Mean set to: ", "SD set to: ", "Reads on same
+//                edge: "), or "No insert-size found for dataset: d"; and
+//                getBaseByBaseCoverage of every edge of every list in list order
+//                as "src dst orient offset nreads coverageDepth SD coverageDepth
+//                SD" lines to <prefix>.coverage: first from the one device call
+//                over all edges, then from the per-edge host mirror
+//                (MG_DEVICE_PLACES=0 or no device: the host mirrors throughout);
 //   -xchg <K>    the exchange mode over RCCL: one
 //                process per GPU (RANK / WORLD_SIZE / LOCAL_RANK / MASTER_ADDR /
 //                MASTER_PORT as torchrun --no-python sets them; none set = one
@@ -263,9 +272,41 @@ static void save_contigs(OverlapGraph* g, Dataset* ds, const std::string& prefix
   std::fclose(f);
 }
 
+// main.cpp:59's statistic with the reference's stdout lines (:1183, :1205-1207), and every edge's coverage
+static void save_insert(OverlapGraph* g, Dataset* ds, size_t n_pe, const std::string& prefix) {
+  g->calculateMeanAndSdOfInsertSize();
+  for (size_t d = 0; d < n_pe; ++d) {
+    if (g->getNumberOfInsertSizes(d) == 0) {
+      std::printf("No insert-size found for dataset: %llu\n", (unsigned long long)d);
+      continue;
+    }
+    std::printf("Mean set to: %llu\nSD set to: %llu\nReads on same edge: %llu\n", (unsigned long long)g->getMean(d),
+                (unsigned long long)g->getSD(d), (unsigned long long)g->getNumberOfInsertSizes(d));
+  }
+  g->calculateCoverageOfAllEdges();
+  const std::string path = prefix + ".coverage";
+  FILE* f = std::fopen(path.c_str(), "w");
+  if (!f) throw std::runtime_error("Unable to open file: " + path);
+  for (UINT64 u = 1; u <= ds->getNumberOfUniqueReads(); ++u) {
+    const std::vector<Edge*>* list = g->getEdges(u);
+    for (size_t j = 0; list && j < list->size(); ++j) {
+      Edge* e = list->at(j);
+      const UINT64 depth = e->coverageDepth, sd = e->SD;
+      g->getBaseByBaseCoverage(e);
+      std::fprintf(f, "%llu %llu %d %llu %llu %llu %llu %llu %llu\n",
+                   (unsigned long long)e->getSourceRead()->getReadNumber(),
+                   (unsigned long long)e->getDestinationRead()->getReadNumber(), (int)e->getOrientation(),
+                   (unsigned long long)e->getOverlapOffset(), (unsigned long long)e->getListOfReads()->size(),
+                   (unsigned long long)depth, (unsigned long long)sd, (unsigned long long)e->coverageDepth,
+                   (unsigned long long)e->SD);
+    }
+  }
+  std::fclose(f);
+}
+
 static void usage() {
   std::fprintf(stderr,
-               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-contigs] [-nocontract | -raw | -s | -xchg K "
+               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-contigs] [-insert] [-nocontract | -raw | -s | -xchg K "
                "[-xchg-sim P] [-xchg-caps F]]\n");
 }
 
@@ -274,7 +315,7 @@ int main(int argc, char** argv) {
   std::string prefix;
   unsigned long long l = 0;
   int k = 0, dev = 0;
-  bool raw = false, nocontract = false, resume = false, mates = false, contigs = false;
+  bool raw = false, nocontract = false, resume = false, mates = false, contigs = false, insert = false;
   int xchg_steps = -1, xchg_sim = 0;
   double xchg_caps = 1.0;
   for (int i = 1; i < argc; ++i) {
@@ -300,6 +341,8 @@ int main(int argc, char** argv) {
       mates = true;
     } else if (a == "-contigs") {
       contigs = true;
+    } else if (a == "-insert") {
+      insert = true;
     } else if (a == "-xchg" && i + 1 < argc) {
       xchg_steps = std::max(0, std::atoi(argv[++i]));
     } else if (a == "-xchg-sim" && i + 1 < argc) {
@@ -340,6 +383,7 @@ int main(int argc, char** argv) {
       g->saveGraphLists(prefix + ".resumed.graph");
       if (mates) save_mates(ds, prefix + ".resumed.mates");
       if (contigs) save_contigs(g, ds, prefix);
+      if (insert) save_insert(g, ds, pe.size(), prefix);
       std::printf("{\"unique_reads\": %llu, \"nodes\": %llu, \"directed_edges\": %llu}\n",
                   (unsigned long long)ds->getNumberOfUniqueReads(), (unsigned long long)g->getNumberOfNodes(),
                   (unsigned long long)g->getNumberOfEdges());
@@ -360,6 +404,7 @@ int main(int argc, char** argv) {
       g->sortEdges();  // main.cpp:49-50
       g->saveGraphToFile(prefix + ".unitig");
       if (contigs) save_contigs(g, ds, prefix);
+      if (insert) save_insert(g, ds, pe.size(), prefix);
     }
     const mg_timings& t = g->timings();
     std::printf(

@@ -32,6 +32,10 @@ MATE_DTYPE = np.dtype([("id", "<u4"), ("orient", "u1"), ("dataset", "u1"), ("pad
 CONTIG_EDGE_DTYPE = np.dtype({"names": ["src", "dst", "offset", "first", "n", "tail", "orient"],
                               "formats": ["<u4", "<u4", "<u8", "<u8", "<u4", "<u4", "u1"],
                               "offsets": [0, 4, 8, 16, 24, 28, 32], "itemsize": 40})
+# one placement of a read on an edge (mg_place, include/mg_overlap.h): 16 bytes
+PLACE_DTYPE = np.dtype([("edge", "<u4"), ("flags", "<u4"), ("distance", "<u8")])
+# the reference's bound on an insert size (OverlapGraph.cpp:1168)
+MAX_INSERT_DISTANCE = 1000
 
 
 class MgError(RuntimeError):
@@ -161,6 +165,15 @@ def lib() -> C.CDLL:
         "mgh_graph_contig_edges": (u64, [vp, i32, vp, u64, vp, vp, vp, u64, P(u64)]),
         "mgh_contigs_build": (i32, [vp, vp, u64, u32, vp, u64, vp, vp, vp, u64, vp, vp, u64, P(u64), C.c_char_p, u64]),
         "mgh_graph_print": (i32, [vp, vp, vp, u64, u32, vp, vp, C.c_char_p, C.c_char_p, C.c_char_p, u64]),
+        "mg_build_placements": (i32, [vp, vp, u64, vp, vp, vp, u64, P(u64), P(C.c_float)]),
+        "mg_copy_placements": (i32, [vp, vp, vp, u64, P(u64)]),
+        "mg_insert_sizes": (i32, [vp, vp, vp, u32, u64, vp, P(C.c_float)]),
+        "mg_edge_coverage": (i32, [vp, vp, vp, P(C.c_float)]),
+        "mgh_placements_build": (i32, [u64, vp, u64, vp, vp, vp, u64, vp, vp, u64, vp, P(u64), C.c_char_p, u64]),
+        "mgh_insert_sizes": (i32, [u64, vp, vp, vp, vp, u32, u64, vp, C.c_char_p, u64]),
+        "mgh_edge_coverage": (i32, [vp, u64, vp, u64, vp, vp, vp, u64, vp, vp, C.c_char_p, u64]),
+        "mgh_mean_sd": (None, [u64, u64, u64, P(u64), P(u64)]),
+        "mgh_graph_read_locations": (u64, [vp, P(u64), vp, vp, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -552,6 +565,69 @@ class OverlapEngine:
         self._check(lib().mg_copy_contigs(self._h, _ptr(start), _ptr(out), total.value, C.byref(got)), "copy_contigs")
         return start, out[: got.value].tobytes()
 
+    # --- read placements, insert sizes and edge coverage
+    def build_placements(self, edges: np.ndarray, reads: np.ndarray, offs: np.ndarray, ors: np.ndarray) -> int:
+        """mg_build_placements (updateReadLocations of every edge): `edges` and
+        the lists as UnitigGraph.contig_edges(all_edges=True) gives them.  Returns
+        the number of placements; places_ms keeps the device time of the kernels.
+        A read ID outside 1..n_reads raises MgError naming the edge and entry (-2)."""
+        edges, reads, offs, ors = _contig_args(edges, reads, offs, ors)
+        n, ms = C.c_uint64(), C.c_float()
+        self._n_places, self._n_place_edges = 0, 0
+        self._check(lib().mg_build_placements(self._h, _ptr(edges), edges.shape[0], _ptr(reads), _ptr(offs), _ptr(ors),
+                                              reads.shape[0], C.byref(n), C.byref(ms)), "build_placements")
+        self.places_ms = float(ms.value)
+        self._n_places, self._n_place_edges = int(n.value), int(edges.shape[0])
+        return self._n_places
+
+    def placements(self):
+        """(start uint64[n_reads + 2], records[PLACE_DTYPE]): the placements of read
+        A = records[start[A]:start[A + 1]] in ascending (edge, list position)."""
+        n = getattr(self, "_n_places", 0)
+        start = np.zeros(int(lib().mg_num_reads(self._h)) + 2, dtype=np.uint64)
+        recs = np.zeros(n, dtype=PLACE_DTYPE)
+        got = C.c_uint64()
+        self._check(lib().mg_copy_placements(self._h, _ptr(start), _ptr(recs), n, C.byref(got)), "copy_placements")
+        return start, recs[: got.value]
+
+    def insert_size_sums(self, n_datasets: int, mates=None, max_distance: int = MAX_INSERT_DISTANCE) -> np.ndarray:
+        """mg_insert_sizes: uint64[n_datasets, 3] = count, sum and sum of squares
+        of the insert sizes per dataset (mean_sd finishes them).  mates = None:
+        the resident lists of build_mate_pairs; else a (start, records) CSR as
+        mate_lists returns.  insert_ms keeps the kernel's device time."""
+        sums = np.zeros((n_datasets, 3), dtype=np.uint64)
+        ms = C.c_float()
+        if mates is None:
+            rc = lib().mg_insert_sizes(self._h, None, None, n_datasets, max_distance, _ptr(sums), C.byref(ms))
+        else:
+            mstart = np.ascontiguousarray(mates[0], dtype=np.uint64)
+            recs = np.ascontiguousarray(mates[1], dtype=MATE_DTYPE)
+            if mstart.shape[0] != int(lib().mg_num_reads(self._h)) + 2 or (mstart.shape[0] and
+                                                                           int(mstart[-1]) > recs.shape[0]):
+                raise MgError("insert_size_sums: the mate CSR does not fit the resident reads")
+            rc = lib().mg_insert_sizes(self._h, _ptr(mstart), _ptr(recs), n_datasets, max_distance, _ptr(sums),
+                                       C.byref(ms))
+        self._check(rc, "insert_sizes")
+        self.insert_ms = float(ms.value)
+        return sums
+
+    def edge_coverage(self, freq=None) -> np.ndarray:
+        """mg_edge_coverage over the edges of the last build_placements:
+        uint64[n_edges, 3] = count, sum and sum of squares over each edge's
+        non-zero per-base counters (getBaseByBaseCoverage; mean_sd finishes
+        them).  freq = frequency per read ID (freq[id - 1]), or None: the
+        frequencies the device ingest left.  coverage_ms keeps the device time."""
+        out = np.zeros((getattr(self, "_n_place_edges", 0), 3), dtype=np.uint64)
+        ms = C.c_float()
+        if freq is not None:
+            freq = np.ascontiguousarray(freq, dtype=np.uint32)
+            if freq.shape[0] != int(lib().mg_num_reads(self._h)):
+                raise MgError("edge_coverage: one frequency per resident read")
+        self._check(lib().mg_edge_coverage(self._h, None if freq is None else _ptr(freq), _ptr(out), C.byref(ms)),
+                    "edge_coverage")
+        self.coverage_ms = float(ms.value)
+        return out
+
     # --- connected components of the lists, labelled on the device
     def build_components(self) -> int:
         """mg_build_components: label every read with the smallest read ID its
@@ -811,6 +887,69 @@ def host_contigs(words: np.ndarray, lens: np.ndarray, edges: np.ndarray, reads: 
     return start, out[: total.value].tobytes()
 
 
+def mean_sd(count: int, total: int, sumsq: int):
+    """(mean, sd, count) from count, sum and sum of squares as the reference
+    finishes them (mgh_mean_sd: integer mean, wrapping 64-bit variance, sd
+    truncated from a double); count == 0 gives (0, 0, 0)."""
+    m, sd = C.c_uint64(), C.c_uint64()
+    lib().mgh_mean_sd(int(count), int(total), int(sumsq), C.byref(m), C.byref(sd))
+    return int(m.value), int(sd.value), int(count)
+
+
+def host_placements(n_reads: int, edges, reads, offs, ors):
+    """mg::placements_build (mgh_placements_build): the host mirror of
+    build_placements + placements.  Returns (start, records, fwd_count)."""
+    edges, reads, offs, ors = _contig_args(edges, reads, offs, ors)
+    start = np.zeros(n_reads + 2, dtype=np.uint64)
+    fwd = np.zeros(n_reads + 2, dtype=np.uint32)
+    n = C.c_uint64()
+    err = C.create_string_buffer(512)
+    args = (n_reads, _ptr(edges), edges.shape[0], _ptr(reads), _ptr(offs), _ptr(ors), reads.shape[0])
+    rc = lib().mgh_placements_build(*args, None, None, 0, None, C.byref(n), err, 512)
+    recs = np.zeros(n.value, dtype=PLACE_DTYPE)
+    if rc == 0:
+        rc = lib().mgh_placements_build(*args, _ptr(start), _ptr(recs), n.value, _ptr(fwd), C.byref(n), err, 512)
+    if rc:
+        raise MgError(f"host_placements: {err.value.decode() or 'bad arguments'} ({rc})")
+    return start, recs, fwd
+
+
+def host_insert_size_sums(places, mates, n_datasets: int, max_distance: int = MAX_INSERT_DISTANCE) -> np.ndarray:
+    """mg::insert_sizes (mgh_insert_sizes): the host mirror of
+    insert_size_sums over a placement CSR and a mate CSR ((start, records) each)."""
+    pstart = np.ascontiguousarray(places[0], dtype=np.uint64)
+    precs = np.ascontiguousarray(places[1], dtype=PLACE_DTYPE)
+    mstart = np.ascontiguousarray(mates[0], dtype=np.uint64)
+    mrecs = np.ascontiguousarray(mates[1], dtype=MATE_DTYPE)
+    if pstart.shape[0] < 2 or mstart.shape[0] != pstart.shape[0] or int(pstart[-1]) > precs.shape[0] or \
+            int(mstart[-1]) > mrecs.shape[0]:
+        raise MgError("host_insert_size_sums: the two CSRs do not fit each other")
+    sums = np.zeros((n_datasets, 3), dtype=np.uint64)
+    err = C.create_string_buffer(512)
+    rc = lib().mgh_insert_sizes(pstart.shape[0] - 2, _ptr(pstart), _ptr(precs), _ptr(mstart), _ptr(mrecs), n_datasets,
+                                max_distance, _ptr(sums), err, 512)
+    if rc:
+        raise MgError(f"host_insert_size_sums: {err.value.decode() or 'bad arguments'} ({rc})")
+    return sums
+
+
+def host_edge_coverage(lens: np.ndarray, freq: np.ndarray, edges, reads, offs, ors) -> np.ndarray:
+    """mg::edge_coverage (mgh_edge_coverage): the host mirror of
+    build_placements + edge_coverage; lens[id - 1], freq[id - 1]."""
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    freq = np.ascontiguousarray(freq, dtype=np.uint32)
+    if freq.shape[0] != lens.shape[0]:
+        raise MgError("host_edge_coverage: one frequency per read")
+    edges, reads, offs, ors = _contig_args(edges, reads, offs, ors)
+    out = np.zeros((edges.shape[0], 3), dtype=np.uint64)
+    err = C.create_string_buffer(512)
+    rc = lib().mgh_edge_coverage(_ptr(lens), lens.shape[0], _ptr(edges), edges.shape[0], _ptr(reads), _ptr(offs),
+                                 _ptr(ors), reads.shape[0], _ptr(freq), _ptr(out), err, 512)
+    if rc:
+        raise MgError(f"host_edge_coverage: {err.value.decode() or 'bad arguments'} ({rc})")
+    return out
+
+
 def read_pairs(files: Sequence[str] | None = None, data: bytes | None = None):
     """The mates of every pair as storeMatePairInformation's loop reads them
     (mgh_read_pairs; `data`: one file's bytes).  Returns (text bytes, offsets
@@ -1020,6 +1159,53 @@ class UnitigGraph:
         L.mgh_graph_contig_edges(self._g, int(all_edges), _ptr(e), n, _ptr(reads), _ptr(offs), _ptr(ors), nl.value,
                                  C.byref(nl))
         return e, reads, offs, ors
+
+    def read_locations(self):
+        """(start uint64[n_reads + 2], records[PLACE_DTYPE]): the read locations the
+        contraction (or readGraphFromFile) tracked, as placements on the edges of
+        contig_edges(all_edges=True), each read's records sorted by (edge,
+        distance, flags).  None when the handle tracked none."""
+        nr = C.c_uint64(0)
+        n = int(self._L.mgh_graph_read_locations(self._g, C.byref(nr), None, None, 0))
+        if not nr.value:
+            return None
+        start = np.zeros(nr.value + 2, dtype=np.uint64)
+        recs = np.zeros(n, dtype=PLACE_DTYPE)
+        self._L.mgh_graph_read_locations(self._g, C.byref(nr), _ptr(start), _ptr(recs), n)
+        return start, recs
+
+    def insert_sizes(self, mates, n_datasets: int, engine=None, max_distance: int = MAX_INSERT_DISTANCE):
+        """calculateMeanAndSdOfInsertSize (OverlapGraph.cpp:1124-1211) over this
+        graph's edges: [(mean, sd, count)] per dataset.  mates = a (start, records)
+        mate CSR, or None with an engine that holds build_mate_pairs' lists.  With
+        an engine that holds the reads the placements and the sums are built on
+        the device, otherwise by the host mirrors."""
+        args = self.contig_edges(all_edges=True)
+        if engine is not None:
+            engine.build_placements(*args)
+            sums = engine.insert_size_sums(n_datasets, mates, max_distance)
+        else:
+            if mates is None:
+                raise MgError("insert_sizes: the host mirror needs the mate lists")
+            start, recs, _ = host_placements(np.asarray(mates[0]).shape[0] - 2, *args)
+            sums = host_insert_size_sums((start, recs), mates, n_datasets, max_distance)
+        return [mean_sd(*(int(x) for x in row)) for row in sums]
+
+    def edge_coverage(self, lens=None, freq=None, engine=None):
+        """getBaseByBaseCoverage (OverlapGraph.cpp:2722-2792) of every edge of
+        contig_edges(all_edges=True): [(coverageDepth, SD, non-zero bases)] per
+        edge.  With an engine that holds the reads: one device call (freq = None
+        takes the ingest's frequencies); otherwise the host mirror over lens and
+        freq (per read ID)."""
+        args = self.contig_edges(all_edges=True)
+        if engine is not None:
+            engine.build_placements(*args)
+            sums = engine.edge_coverage(freq)
+        else:
+            if lens is None or freq is None:
+                raise MgError("edge_coverage: the host mirror needs lens and freq")
+            sums = host_edge_coverage(lens, freq, *args)
+        return [mean_sd(*(int(x) for x in row)) for row in sums]
 
     def print_graph(self, ds, gdl: str, fasta: str, engine=None):
         """printGraph (OverlapGraph.cpp:428-520): the .gdl file and the contigs as
