@@ -10,7 +10,12 @@ lists built on the device, against the reference's own lists
   c. the refusals and the not-found error, their codes and messages;
   d. the lists survive mg_find_overlaps and are invalidated by a new ingest;
   e. the drop-in: Read::getMatePairList() after new OverlapGraph(ht)
-     (test_mates_dropin.py)."""
+     (test_mates_dropin.py);
+  f. the word edges of the redirected-mate substring test (mates of 11-65 bp
+     at the first, last and word-edge offsets of containers of every slot
+     width, forward near-misses), 256 datasets, a 3,000-entry list, runs of
+     1,000 equal records and the pair counts 0 .. 257: test_mate_edges.py on
+     the sets of mate_sets.py, whose host mirror test_mate_edges_host.py pins."""
 import numpy as np
 import pytest
 
