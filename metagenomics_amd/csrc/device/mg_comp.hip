@@ -55,13 +55,11 @@
 #include <cstdint>
 #include <string>
 
-#include "mg_ctx.hpp"
 #include "mg_overlap.h"
+#include "mg_stage.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
 constexpr int kWaveReads = 32;   // consecutive reads one wavefront of k_comp_hook takes
 constexpr int kSumReads = 4096;  // consecutive reads one workgroup of k_comp_sums takes
 constexpr int kSumSlotsLog2 = 9;
@@ -204,69 +202,61 @@ __global__ __launch_bounds__(kThreads) void k_comp_table(const uint32_t* __restr
   if (at < n_comp) out[at] = mg_comp{(uint32_t)r, acc_reads[r], acc_disc[r], acc_self[r]};
 }
 
-inline uint32_t blocks_for(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, (items + kThreads - 1) / kThreads); }
-
 int label_components(mg_ctx* ctx) {
   const uint64_t N = ctx->n, entries = N + 2;
-  ctx->n_comp = 0;
-  MG_ENSURE(d_comp_parent, comp_parent_cap, entries);
-  MG_ENSURE(d_comp_label, comp_label_cap, entries);
-  MG_ENSURE(d_comp_acc, comp_acc_cap, 2 * entries);
-  if (ctx->disc_cnt_cap < entries || !ctx->d_disc_cnt || ctx->disc_start_cap < entries || !ctx->d_disc_start ||
-      (ctx->n_disc && (!ctx->d_disc || ctx->disc_cap < ctx->n_disc)))
+  DiscStage& ds = ctx->disc;  // its lists are the input; its count array and temporary storage are borrowed
+  CompStage& cs = ctx->comp;
+  cs.n = 0;
+  MG_GROW(cs.parent, entries, "d_comp_parent");
+  MG_GROW(cs.label, entries, "d_comp_label");
+  MG_GROW(cs.acc, 2 * entries, "d_comp_acc");
+  if (ds.cnt.cap < entries || !ds.cnt.p || ds.start.cap < entries || !ds.start.p ||
+      (ds.n && (!ds.recs.p || ds.recs.cap < ds.n)))
     return set_err(ctx, "mg_build_components: the discovery-list buffers are missing");
-  uint32_t* self_cnt = ctx->d_disc_cnt;  // (free after mg_build_discoveries) self records per read, then the scan's output
-  uint32_t* acc_reads = ctx->d_comp_parent;  // (after the flatten)
-  uint32_t* acc_disc = ctx->d_comp_acc;
-  uint32_t* acc_self = ctx->d_comp_acc + entries;
+  uint32_t* self_cnt = ds.cnt.p;  // (free after mg_build_discoveries) self records per read, then the scan's output
+  uint32_t* acc_reads = cs.parent.p;  // (after the flatten)
+  uint32_t* acc_disc = cs.acc.p;
+  uint32_t* acc_self = cs.acc.p + entries;
   auto flags = rocprim::make_transform_iterator(acc_disc, CompFlag());
   size_t tb = 0;
   MG_TRY(rocprim::exclusive_scan(nullptr, tb, flags, self_cnt, 0u, (size_t)entries, rocprim::plus<uint32_t>(),
                                  ctx->stream));
-  MG_ENSURE(d_disc_tmp, disc_tmp_cap, tb);
-  tb = ctx->disc_tmp_cap;
+  MG_GROW(ds.tmp, tb, "d_disc_tmp");
+  tb = ds.tmp.cap;
 
-  hipLaunchKernelGGL(k_comp_init, dim3(blocks_for(entries)), dim3(kThreads), 0, ctx->stream, ctx->d_comp_parent,
+  hipLaunchKernelGGL(k_comp_init, dim3(blocks_for(entries)), dim3(kThreads), 0, ctx->stream, cs.parent.p,
                      self_cnt, entries);
   MG_TRY(hipGetLastError());
-  if (N && ctx->n_disc) {
+  if (N && ds.n) {
     const uint64_t waves = (N + kWaveReads - 1) / kWaveReads;
-    hipLaunchKernelGGL(k_comp_hook, dim3(blocks_for(waves * kWave)), dim3(kThreads), 0, ctx->stream, ctx->d_disc,
-                       ctx->d_disc_start, (uint32_t)N, ctx->d_comp_parent, self_cnt);
+    hipLaunchKernelGGL(k_comp_hook, dim3(blocks_for(waves * kWave)), dim3(kThreads), 0, ctx->stream, ds.recs.p,
+                       ds.start.p, (uint32_t)N, cs.parent.p, self_cnt);
     MG_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_comp_flatten, dim3(blocks_for(N + 1)), dim3(kThreads), 0, ctx->stream, ctx->d_comp_parent,
-                     (uint32_t)N, ctx->d_comp_label);
+  hipLaunchKernelGGL(k_comp_flatten, dim3(blocks_for(N + 1)), dim3(kThreads), 0, ctx->stream, cs.parent.p,
+                     (uint32_t)N, cs.label.p);
   MG_TRY(hipGetLastError());
-  if (!N || !ctx->n_disc) return 0;
+  if (!N || !ds.n) return 0;
   MG_TRY(hipMemsetAsync(acc_reads, 0, entries * sizeof(uint32_t), ctx->stream));
-  MG_TRY(hipMemsetAsync(ctx->d_comp_acc, 0, 2 * entries * sizeof(uint32_t), ctx->stream));
+  MG_TRY(hipMemsetAsync(cs.acc.p, 0, 2 * entries * sizeof(uint32_t), ctx->stream));
   const uint32_t sum_blocks = (uint32_t)((N + kSumReads - 1) / kSumReads);
   hipLaunchKernelGGL(k_comp_sums, dim3(sum_blocks), dim3(kThreads), 0, ctx->stream,
-                     ctx->d_comp_label, ctx->d_disc_start, self_cnt, (uint32_t)N, acc_reads, acc_disc, acc_self);
+                     cs.label.p, ds.start.p, self_cnt, (uint32_t)N, acc_reads, acc_disc, acc_self);
   MG_TRY(hipGetLastError());
-  MG_TRY(rocprim::exclusive_scan(ctx->d_disc_tmp, tb, flags, self_cnt, 0u, (size_t)entries,
+  MG_TRY(rocprim::exclusive_scan(ds.tmp.p, tb, flags, self_cnt, 0u, (size_t)entries,
                                  rocprim::plus<uint32_t>(), ctx->stream));
   uint32_t count = 0;  // (entry N + 1 is no root: the exclusive sum there is the total)
   MG_TRY(hipMemcpyAsync(&count, self_cnt + N + 1, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
-  MG_ENSURE(d_comp, comp_cap, count);
+  MG_GROW(cs.table, count, "d_comp");
   hipLaunchKernelGGL(k_comp_table, dim3(blocks_for(N)), dim3(kThreads), 0, ctx->stream, acc_reads, acc_disc, acc_self,
-                     self_cnt, (uint32_t)N, (uint64_t)count, ctx->d_comp);
+                     self_cnt, (uint32_t)N, (uint64_t)count, cs.table.p);
   MG_TRY(hipGetLastError());
-  ctx->n_comp = count;
+  cs.n = count;
   return 0;
 }
 
 }  // namespace
-
-void comp_release(mg_ctx* ctx) {
-  void* bufs[] = {ctx->d_comp_parent, ctx->d_comp_label, ctx->d_comp_acc, ctx->d_comp};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (auto& e : ctx->comp_ev)
-    if (e) (void)hipEventDestroy(e);
-}
 
 extern "C" {
 
@@ -276,20 +266,18 @@ int mg_build_components(mg_ctx* ctx, uint64_t* n_comp, float* device_ms) {
   MG_TRY(hipSetDevice(ctx->device));
   if (n_comp) *n_comp = 0;
   if (device_ms) *device_ms = 0.f;
-  ctx->comp_ready = false;
+  ctx->comp.ready = false;
   if (whole_multiset(ctx, "mg_build_components")) return -1;
-  if (!ctx->index_ready || !ctx->rows_found || !ctx->disc_ready)
+  if (!ctx->index_ready || !ctx->rows_found || !ctx->disc.ready)
     return set_err(ctx, "mg_build_components: mg_build_discoveries must run for the current rows first");
-  for (auto& e : ctx->comp_ev)
-    if (!e) MG_TRY(hipEventCreate(&e));
-  MG_TRY(hipEventRecord(ctx->comp_ev[0], ctx->stream));
+  MG_TRY(ctx->comp.ev.start(ctx->stream));
   const int rc = label_components(ctx);
   if (rc) return rc;
-  MG_TRY(hipEventRecord(ctx->comp_ev[1], ctx->stream));
-  MG_TRY(hipEventSynchronize(ctx->comp_ev[1]));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->comp_ev[0], ctx->comp_ev[1]));
-  ctx->comp_ready = true;
-  if (n_comp) *n_comp = ctx->n_comp;
+  MG_TRY(ctx->comp.ev.end(ctx->stream));
+  MG_TRY(ctx->comp.ev.wait());
+  MG_TRY(ctx->comp.ev.elapsed(device_ms));
+  ctx->comp.ready = true;
+  if (n_comp) *n_comp = ctx->comp.n;
   return 0;
 }
 
@@ -299,16 +287,9 @@ int mg_copy_components(mg_ctx* ctx, uint32_t* label, mg_comp* comps, uint64_t ca
   MG_TRY(hipSetDevice(ctx->device));
   if (n_copied) *n_copied = 0;
   if (whole_multiset(ctx, "mg_copy_components")) return -1;
-  if (!ctx->index_ready || !ctx->rows_found || !ctx->disc_ready || !ctx->comp_ready)
+  if (!ctx->index_ready || !ctx->rows_found || !ctx->disc.ready || !ctx->comp.ready)
     return set_err(ctx, "mg_copy_components: mg_build_components must run for the current lists first");
-  if (label)
-    MG_TRY(hipMemcpyAsync(label, ctx->d_comp_label, (ctx->n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-  const uint64_t c = comps ? std::min(cap, ctx->n_comp) : 0;
-  if (c) MG_TRY(hipMemcpyAsync(comps, ctx->d_comp, c * sizeof(mg_comp), hipMemcpyDeviceToHost, ctx->stream));
-  MG_TRY(hipStreamSynchronize(ctx->stream));
-  if (n_copied) *n_copied = c;
-  return 0;
+  return copy_csr(ctx, ctx->comp.label.p, ctx->n + 1, label, ctx->comp.table.p, ctx->comp.n, comps, cap, n_copied);
 }
 
 }  // extern "C"

@@ -28,13 +28,11 @@
 #include <string>
 #include <vector>
 
-#include "mg_ctx.hpp"
 #include "mg_overlap.h"
+#include "mg_stage.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
 // LDS staging span of one wavefront (one 64-thread workgroup), bytes.  A
 // sub-run of pieces is staged when its bases fit; a single piece above it takes
 // the wavefront-per-piece path.  4 KiB + one word per workgroup keeps 32
@@ -42,14 +40,6 @@ constexpr int kWave = 64;
 constexpr uint32_t kSpan = 4096;
 
 constexpr uint8_t kFwd = 1, kN = 2;
-
-struct ReadView {
-  const uint64_t* words;
-  const uint16_t* len;
-  const uint32_t* phys;  // slot of ID - 1, or nullptr (slots in ID order)
-  uint64_t n;
-  uint32_t stride;
-};
 
 __device__ __forceinline__ uint64_t desc_of(uint64_t slot, uint32_t pos, uint32_t len) {
   return slot | (uint64_t)pos << 32 | (uint64_t)len << 48;
@@ -238,27 +228,6 @@ __global__ __launch_bounds__(kWave) void k_ctg_copy(ReadView v, const uint64_t* 
   }
 }
 
-uint32_t blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + kThreads - 1) / kThreads); }
-
-}  // namespace
-
-void contigs_release(mg_ctx* ctx) {
-  void* bufs[] = {ctx->d_ctg_desc, ctx->d_ctg_flag, ctx->d_ctg_len,  ctx->d_ctg_pos, ctx->d_ctg_pbase,
-                  ctx->d_ctg_start, ctx->d_ctg_out, ctx->d_ctg_tmp, ctx->d_ctg_ctl};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (auto& e : ctx->ctg_ev)
-    if (e) (void)hipEventDestroy(e);
-}
-
-namespace {
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
 }  // namespace
 
 extern "C" {
@@ -270,99 +239,75 @@ int mg_build_contigs(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edges,
   ctx->err.clear();
   if (total_bases) *total_bases = 0;
   if (device_ms) *device_ms = 0.f;
-  ctx->contigs_ready = false;
+  ctx->contigs.ready = false;
   if ((n_edges && !edges) || (n_list && (!reads || !offs || !ors))) return set_err(ctx, "mg_build_contigs: null argument");
   MG_TRY(hipSetDevice(ctx->device));
   if (!ctx->n || !ctx->d_words || !ctx->d_len) return set_err(ctx, "mg_build_contigs: no reads on the device");
   // first piece of every edge; list ranges must lie inside the lists
-  std::vector<uint64_t> pbase(n_edges + 1, 0);
-  for (uint64_t k = 0; k < n_edges; ++k) {
-    if (edges[k].first > n_list || edges[k].n > n_list - edges[k].first)
-      return set_err(ctx, "mg_build_contigs: edge " + std::to_string(k) + " (" + std::to_string(edges[k].src) + ", " +
-                              std::to_string(edges[k].dst) + "): its list range lies outside the " +
-                              std::to_string(n_list) + " list entries");
-    pbase[k + 1] = pbase[k] + edges[k].n + 2;
-  }
+  std::vector<uint64_t> pbase;
+  if (edge_bases(ctx, "mg_build_contigs", edges, n_edges, n_list, 2, pbase)) return -1;
   const uint64_t P = pbase[n_edges];
-  for (auto& e : ctx->ctg_ev)
-    if (!e) MG_TRY(hipEventCreate(&e));
   hipStream_t st = ctx->stream;
-  MG_ENSURE(d_ctg_desc, ctg_desc_cap, P);
-  MG_ENSURE(d_ctg_flag, ctg_flag_cap, P);
-  MG_ENSURE(d_ctg_len, ctg_len_cap, P + 1);
-  MG_ENSURE(d_ctg_pos, ctg_pos_cap, P + 1);
-  MG_ENSURE(d_ctg_pbase, ctg_pbase_cap, n_edges + 1);
-  MG_ENSURE(d_ctg_start, ctg_start_cap, n_edges + 1);
-  MG_ENSURE(d_ctg_ctl, ctg_ctl_cap, 1);
+  ContigStage& cg = ctx->contigs;
+  MG_GROW(cg.desc, P, "d_ctg_desc");
+  MG_GROW(cg.flag, P, "d_ctg_flag");
+  MG_GROW(cg.len, P + 1, "d_ctg_len");
+  MG_GROW(cg.pos, P + 1, "d_ctg_pos");
+  MG_GROW(cg.pbase, n_edges + 1, "d_ctg_pbase");
+  MG_GROW(cg.start, n_edges + 1, "d_ctg_start");
+  MG_GROW(cg.ctl, 1, "d_ctg_ctl");
   size_t tmp_bytes = 0;
-  MG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, ctx->d_ctg_len, ctx->d_ctg_pos, (int64_t)(P + 1), st));
-  MG_ENSURE(d_ctg_tmp, ctg_tmp_cap, tmp_bytes);
+  MG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, cg.len.p, cg.pos.p, (int64_t)(P + 1), st));
+  MG_GROW(cg.tmp, tmp_bytes, "d_ctg_tmp");
   // the caller's lists, for the length kernel only
-  DevBuf<mg_contig_edge> d_edges;
-  DevBuf<uint32_t> d_reads;
-  DevBuf<uint16_t> d_offs;
-  DevBuf<uint8_t> d_ors;
-  if (ctx_malloc(ctx, reinterpret_cast<void**>(&d_edges.p), n_edges * sizeof(mg_contig_edge), "contig edges") !=
-          hipSuccess ||
-      ctx_malloc(ctx, reinterpret_cast<void**>(&d_reads.p), n_list * sizeof(uint32_t), "contig list reads") !=
-          hipSuccess ||
-      ctx_malloc(ctx, reinterpret_cast<void**>(&d_offs.p), n_list * sizeof(uint16_t), "contig list offsets") !=
-          hipSuccess ||
-      ctx_malloc(ctx, reinterpret_cast<void**>(&d_ors.p), n_list, "contig list orientations") != hipSuccess)
-    return -1;
+  Scratch<mg_contig_edge> d_edges;
+  EdgeLists lists;
+  MG_SCRATCH(d_edges, n_edges, "contig edges");
   if (n_edges) MG_TRY(hipMemcpyAsync(d_edges.p, edges, n_edges * sizeof(mg_contig_edge), hipMemcpyHostToDevice, st));
-  if (n_list) {
-    MG_TRY(hipMemcpyAsync(d_reads.p, reads, n_list * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    MG_TRY(hipMemcpyAsync(d_offs.p, offs, n_list * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    MG_TRY(hipMemcpyAsync(d_ors.p, ors, n_list, hipMemcpyHostToDevice, st));
-  }
-  MG_TRY(hipMemcpyAsync(ctx->d_ctg_pbase, pbase.data(), (n_edges + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  const unsigned long long none = ~0ull;
-  MG_TRY(hipMemcpyAsync(ctx->d_ctg_ctl, &none, sizeof(none), hipMemcpyHostToDevice, st));
-  MG_TRY(hipMemsetAsync(ctx->d_ctg_len + P, 0, sizeof(uint64_t), st));
-  const ReadView v{ctx->d_words, ctx->d_len, ctx->d_phys, ctx->n, ctx->stride};
+  if (lists.upload(ctx, "contig", reads, offs, ors, n_list)) return -1;
+  MG_TRY(hipMemcpyAsync(cg.pbase.p, pbase.data(), (n_edges + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  MG_TRY(ctl_fill(st, cg.ctl.p, 1, ~0ull));
+  MG_TRY(hipMemsetAsync(cg.len.p + P, 0, sizeof(uint64_t), st));
+  const ReadView v = view_of(ctx);
 
-  MG_TRY(hipEventRecord(ctx->ctg_ev[0], st));
+  MG_TRY(cg.ev.start(st));
   if (P) {
-    hipLaunchKernelGGL(k_ctg_len, dim3(blocks(P)), dim3(kThreads), 0, st, v, d_edges.p, n_edges, ctx->d_ctg_pbase,
-                       d_reads.p, d_offs.p, d_ors.p, P, ctx->d_ctg_desc, ctx->d_ctg_flag, ctx->d_ctg_len, ctx->d_ctg_ctl);
+    hipLaunchKernelGGL(k_ctg_len, dim3(blocks_for(P)), dim3(kThreads), 0, st, v, d_edges.p, n_edges, cg.pbase.p,
+                       lists.reads.p, lists.offs.p, lists.ors.p, P, cg.desc.p, cg.flag.p, cg.len.p, cg.ctl.p);
     MG_TRY(hipGetLastError());
   }
-  MG_TRY(hipcub::DeviceScan::ExclusiveSum(ctx->d_ctg_tmp, tmp_bytes, ctx->d_ctg_len, ctx->d_ctg_pos, (int64_t)(P + 1),
-                                          st));
-  hipLaunchKernelGGL(k_ctg_start, dim3(blocks(n_edges + 1)), dim3(kThreads), 0, st, ctx->d_ctg_pbase, ctx->d_ctg_pos,
-                     n_edges + 1, ctx->d_ctg_start);
+  MG_TRY(hipcub::DeviceScan::ExclusiveSum(cg.tmp.p, tmp_bytes, cg.len.p, cg.pos.p, (int64_t)(P + 1), st));
+  hipLaunchKernelGGL(k_ctg_start, dim3(blocks_for(n_edges + 1)), dim3(kThreads), 0, st, cg.pbase.p, cg.pos.p,
+                     n_edges + 1, cg.start.p);
   MG_TRY(hipGetLastError());
   // one host read: the error word and the total decide whether and where the copy kernel writes
   unsigned long long bad = ~0ull;
   uint64_t total = 0;
-  MG_TRY(hipMemcpyAsync(&bad, ctx->d_ctg_ctl, sizeof(bad), hipMemcpyDeviceToHost, st));
-  MG_TRY(hipMemcpyAsync(&total, ctx->d_ctg_pos + P, sizeof(total), hipMemcpyDeviceToHost, st));
-  MG_TRY(hipStreamSynchronize(st));
+  MG_TRY(hipMemcpyAsync(&total, cg.pos.p + P, sizeof(total), hipMemcpyDeviceToHost, st));
+  MG_TRY(ctl_read(st, cg.ctl.p, 1, &bad));
   if (bad != ~0ull) {
     const uint64_t k = (uint64_t)(std::upper_bound(pbase.begin(), pbase.end(), (uint64_t)bad) - pbase.begin()) - 1;
     const uint64_t i = bad - pbase[k];
     const std::string which = i == 0 ? "the source read"
                               : i <= edges[k].n ? "list entry " + std::to_string(i - 1)
                                                 : "the destination read";
-    ctx->err = "mg_build_contigs: edge " + std::to_string(k) + " (" + std::to_string(edges[k].src) + ", " +
-               std::to_string(edges[k].dst) + "), piece " + std::to_string(i) + " (" + which +
+    ctx->err = "mg_build_contigs: " + edge_name(edges, k) + ", piece " + std::to_string(i) + " (" + which +
                "): a read ID outside 1.." + std::to_string(ctx->n) +
                " or a substring position outside its read (std::string::substr would throw) (-2)";
     return -2;
   }
-  MG_ENSURE(d_ctg_out, ctg_out_cap, (total + 3) & ~3ull);
+  MG_GROW(cg.out, (total + 3) & ~3ull, "d_ctg_out");
   if (P) {
-    hipLaunchKernelGGL(k_ctg_copy, dim3((uint32_t)((P + kWave - 1) / kWave)), dim3(kWave), 0, st, v, ctx->d_ctg_desc,
-                       ctx->d_ctg_flag, ctx->d_ctg_pos, P, ctx->d_ctg_out);
+    hipLaunchKernelGGL(k_ctg_copy, dim3((uint32_t)((P + kWave - 1) / kWave)), dim3(kWave), 0, st, v, cg.desc.p,
+                       cg.flag.p, cg.pos.p, P, cg.out.p);
     MG_TRY(hipGetLastError());
   }
-  MG_TRY(hipEventRecord(ctx->ctg_ev[1], st));
+  MG_TRY(cg.ev.end(st));
   MG_TRY(hipStreamSynchronize(st));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->ctg_ev[0], ctx->ctg_ev[1]));
-  ctx->n_contig_edges = n_edges;
-  ctx->n_contig_bases = total;
-  ctx->contigs_ready = true;
+  MG_TRY(cg.ev.elapsed(device_ms));
+  cg.n_edges = n_edges;
+  cg.n_bases = total;
+  ctx->contigs.ready = true;
   if (total_bases) *total_bases = total;
   return 0;
 }
@@ -372,16 +317,10 @@ int mg_copy_contigs(mg_ctx* ctx, uint64_t* start, char* out, uint64_t cap, uint6
   ctx->err.clear();
   MG_TRY(hipSetDevice(ctx->device));
   if (n_copied) *n_copied = 0;
-  if (!ctx->contigs_ready)
+  if (!ctx->contigs.ready)
     return set_err(ctx, "mg_copy_contigs: mg_build_contigs must succeed for the current reads first");
-  if (start)
-    MG_TRY(hipMemcpyAsync(start, ctx->d_ctg_start, (ctx->n_contig_edges + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-  const uint64_t c = out ? std::min(cap, ctx->n_contig_bases) : 0;
-  if (c) MG_TRY(hipMemcpyAsync(out, ctx->d_ctg_out, c, hipMemcpyDeviceToHost, ctx->stream));
-  MG_TRY(hipStreamSynchronize(ctx->stream));
-  if (n_copied) *n_copied = c;
-  return 0;
+  const ContigStage& cg = ctx->contigs;
+  return copy_csr(ctx, cg.start.p, cg.n_edges + 1, start, cg.out.p, cg.n_bases, out, cap, n_copied);
 }
 
 }  // extern "C"

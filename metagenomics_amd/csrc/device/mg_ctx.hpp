@@ -3,7 +3,12 @@
 // exchange; mg_dataset.hip: Dataset ingest on the device; mg_disc.hip: the
 // per-read discovery lists D(A); mg_comp.hip: their components; mg_mates.hip:
 // read lookup and the per-read mate lists; mg_contigs.hip: the strings of edges;
-// mg_places.hip: read placements, insert sizes and edge coverage).
+// mg_places.hip: read placements, insert sizes and edge coverage).  The core
+// fields of mg_ctx belong to mg_kernels.hip; each derived stage keeps its
+// state in one struct (DiscStage .. PlaceStage: ready flag, counts, test
+// options, DevArray buffers, EventPair) that mg_ctx embeds by value; their
+// destructors free them when mg_destroy deletes the context.  What the stage files share beyond the context
+// (call-lifetime scratch, the read view, CSR helpers) is in mg_stage.hpp.
 #ifndef MG_CTX_HPP_
 #define MG_CTX_HPP_
 #include <hip/hip_runtime.h>
@@ -32,6 +37,137 @@ static_assert(slot_id_word(5) == 7 && slot_id_word(6) == 7 && slot_id_word(12) =
 static_assert(slot_id_word(1) == -1 && slot_id_word(2) == -1 && slot_id_word(3) == -1 && slot_id_word(4) == -1 &&
                   slot_id_word(8) == -1 && slot_id_word(16) == -1 && slot_id_word(32) == -1,
               "widths whose slot ends at the pad word (or before it)");
+
+// A device array that lives as long as the context and is freed with it
+// (mg_destroy deletes the context with its device set and its stream idle):
+// pointer and capacity travel together (mg_disc.hip swaps two of them whole).
+// The stage files grow one with MG_GROW (below).
+template <typename T>
+struct DevArray {
+  T* p = nullptr;
+  size_t cap = 0;  // elements
+  DevArray() = default;
+  DevArray(const DevArray&) = delete;
+  DevArray& operator=(const DevArray&) = delete;
+  ~DevArray() {
+    if (p) (void)hipFree(p);
+  }
+  // at least `count` elements (contents not kept); `what` names the buffer in the error message
+  hipError_t ensure(mg_ctx* ctx, size_t count, const char* what);
+  void swap(DevArray& o) {
+    std::swap(p, o.p);
+    std::swap(cap, o.cap);
+  }
+};
+
+// The two events a stage times itself with, created on first use, destroyed
+// with the context.
+struct EventPair {
+  hipEvent_t ev[2] = {};
+  EventPair() = default;
+  EventPair(const EventPair&) = delete;
+  EventPair& operator=(const EventPair&) = delete;
+  ~EventPair() {
+    for (auto& e : ev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  hipError_t start(hipStream_t st) {
+    for (auto& e : ev)
+      if (!e) {
+        const hipError_t rc = hipEventCreate(&e);
+        if (rc != hipSuccess) return rc;
+      }
+    return hipEventRecord(ev[0], st);
+  }
+  hipError_t end(hipStream_t st) { return hipEventRecord(ev[1], st); }
+  hipError_t wait() { return hipEventSynchronize(ev[1]); }
+  // (both events completed) device_ms may be null
+  hipError_t elapsed(float* device_ms) { return device_ms ? hipEventElapsedTime(device_ms, ev[0], ev[1]) : hipSuccess; }
+};
+
+// per-read discovery lists D(A) (mg_disc.hip, mg_build_discoveries): the rows
+// of the last mg_find_overlaps grouped by src into a CSR array and each
+// segment sorted by (window j, dst, key o).  ready: the lists belong to those rows
+struct DiscStage {
+  bool ready = false;
+  uint64_t n = 0;          // records
+  uint32_t block_cap = 0;  // option "disc_block_cap" (tests): records the workgroup sort takes (0 = 2,048)
+  DevArray<uint32_t> cnt;    // rows per src, then the scatter's cursors (n + 2)
+  DevArray<uint64_t> start;  // start[A] (n + 2)
+  DevArray<uint64_t> recs;   // one 8-B record per row: the sort key, then the mg_disc record
+  DevArray<uint32_t> list;   // reads of degree > 64: workgroup path from the front, oversized from the back
+  DevArray<uint32_t> boff;   // oversized segments: their offsets in big[]
+  DevArray<uint64_t> big[2];  // oversized segments gathered for the segmented radix sort
+  DevArray<uint8_t> tmp;      // rocprim temporary storage (scans, segmented sort)
+  DevArray<unsigned long long> ctl;  // kDiscCtl control words (errors, class counts, self duplicates)
+  // self rows only (tandem repeats): the duplicate-free copy and its starts, swapped with recs / start
+  DevArray<uint64_t> recs_alt, start_alt;
+  DevArray<uint32_t> pre;  // kept records before each record
+  EventPair ev;
+};
+
+// connected components of the discovery lists (mg_comp.hip, mg_build_components):
+// ready: labels and table belong to the current lists (cleared with disc.ready
+// and by every mg_build_discoveries)
+struct CompStage {
+  bool ready = false;
+  uint64_t n = 0;             // components in the table
+  DevArray<uint32_t> parent;  // union-find parent[0 .. n + 1]; after the flatten: reads per root
+  DevArray<uint32_t> label;   // label[0 .. n + 1], label[0] = 0
+  DevArray<uint32_t> acc;     // per root: records [0, n + 2), self records [n + 2, 2 (n + 2))
+  DevArray<mg_comp> table;    // ascending root
+  EventPair ev;
+};
+
+// per-read mate lists (mg_mates.hip, mg_build_mate_pairs): one CSR of mg_mate
+// records over the reads; ready until new reads arrive (reset_derived)
+struct MateStage {
+  bool ready = false;
+  uint64_t n = 0;            // records
+  DevArray<uint64_t> start;  // start[A] (n + 2)
+  DevArray<mg_mate> recs;
+  EventPair ev;
+};
+
+// contig strings (mg_contigs.hip, mg_build_contigs): one descriptor and one
+// output position per piece, the edges' string starts and the ASCII bases;
+// ready until new reads arrive (reset_derived)
+struct ContigStage {
+  bool ready = false;
+  uint64_t n_edges = 0, n_bases = 0;
+  DevArray<uint64_t> desc;   // per piece: slot | position << 32 | read length << 48
+  DevArray<uint8_t> flag;    // per piece: bit 0 forward strand, bit 1 'N' first
+  DevArray<uint64_t> len;    // per piece: bases it writes (scan input)
+  DevArray<uint64_t> pos;    // per piece (+ 1): where it writes
+  DevArray<uint64_t> pbase;  // per edge (+ 1): its first piece
+  DevArray<uint64_t> start;  // per edge (+ 1): where its string starts
+  DevArray<char> out;
+  DevArray<uint8_t> tmp;     // the scan's temporary storage
+  DevArray<unsigned long long> ctl;  // [0] = first invalid piece
+  EventPair ev;
+};
+
+// read placements (mg_places.hip, mg_build_placements): one CSR of mg_place
+// records over the reads, each read's forward-placement count, and what
+// mg_edge_coverage reads again: the edges and, per list entry of every edge
+// ("entry space", edge k at ebase[k]), its read, edge and distance.
+// ready until new reads arrive (reset_derived)
+struct PlaceStage {
+  bool ready = false;
+  uint64_t n = 0;                     // records
+  std::vector<mg_contig_edge> edges;  // the edges of the last build (messages, chunking)
+  std::vector<uint64_t> ebase;        // per edge (+ 1): its first entry
+  DevArray<uint64_t> start;           // start[A] (n + 2)
+  DevArray<mg_place> recs;
+  DevArray<uint32_t> fwd;  // forward placements of read A (n + 2)
+  DevArray<mg_contig_edge> d_edges;
+  DevArray<uint64_t> d_ebase;
+  DevArray<uint32_t> eread, eedge;
+  DevArray<uint64_t> edist;
+  // option "cov_budget" (tests): per-base counters one chunk of mg_edge_coverage holds (0 = 2^25)
+  uint64_t cov_budget = 0;
+  EventPair ev;
+};
 
 struct mg_ctx {
   int device = 0;
@@ -328,115 +464,16 @@ struct mg_ctx {
   // option "alloc_cap" (tests): a device allocation above this many bytes fails
   // as out of memory (0 = no cap), so the error path is exercised on purpose
   uint64_t alloc_cap = 0;
-  // per-read discovery lists D(A) (mg_disc.hip, mg_build_discoveries): the rows
-  // of the last mg_find_overlaps grouped by src into a CSR array and each
-  // segment sorted by (window j, dst, key o).  rows_found: mg_find_overlaps
-  // completed for the current index; disc_ready: the lists belong to those rows
+  // mg_find_overlaps completed for the current index (the discovery lists need its rows)
   bool rows_found = false;
-  bool disc_ready = false;
-  uint64_t n_disc = 0;
-  uint32_t disc_block_cap = 0;  // option "disc_block_cap" (tests): records the workgroup sort takes (0 = 2,048)
-  uint32_t* d_disc_cnt = nullptr;  // rows per src, then the scatter's cursors (n + 2)
-  size_t disc_cnt_cap = 0;
-  uint64_t* d_disc_start = nullptr;  // start[A] (n + 2)
-  size_t disc_start_cap = 0;
-  uint64_t* d_disc = nullptr;  // one 8-B record per row: the sort key, then the mg_disc record
-  size_t disc_cap = 0;
-  uint32_t* d_disc_list = nullptr;  // reads of degree > 64: workgroup path from the front, oversized from the back
-  size_t disc_list_cap = 0;
-  uint32_t* d_disc_boff = nullptr;  // oversized segments: their offsets in d_disc_big
-  size_t disc_boff_cap = 0;
-  uint64_t* d_disc_big[2] = {nullptr, nullptr};  // oversized segments gathered for the segmented radix sort
-  size_t disc_big_cap[2] = {0, 0};
-  uint8_t* d_disc_tmp = nullptr;  // rocprim temporary storage (scans, segmented sort)
-  size_t disc_tmp_cap = 0;
-  unsigned long long* d_disc_ctl = nullptr;  // kDiscCtl control words (errors, class counts, self duplicates)
-  size_t disc_ctl_cap = 0;
-  // self rows only (tandem repeats): the duplicate-free copy and its starts
-  uint64_t* d_disc_alt = nullptr;
-  size_t disc_alt_cap = 0;
-  uint64_t* d_disc_start_alt = nullptr;
-  size_t disc_start_alt_cap = 0;
-  uint32_t* d_disc_pre = nullptr;  // kept records before each record
-  size_t disc_pre_cap = 0;
-  hipEvent_t disc_ev[2] = {};
-  // connected components of the discovery lists (mg_comp.hip, mg_build_components):
-  // comp_ready: labels and table belong to the current lists (cleared with
-  // disc_ready and by every mg_build_discoveries)
-  bool comp_ready = false;
-  uint64_t n_comp = 0;
-  uint32_t* d_comp_parent = nullptr;  // union-find parent[0 .. n + 1]; after the flatten: reads per root
-  size_t comp_parent_cap = 0;
-  uint32_t* d_comp_label = nullptr;  // label[0 .. n + 1], label[0] = 0
-  size_t comp_label_cap = 0;
-  uint32_t* d_comp_acc = nullptr;  // per root: records [0, n + 2), self records [n + 2, 2 (n + 2))
-  size_t comp_acc_cap = 0;
-  mg_comp* d_comp = nullptr;  // the table, ascending root
-  size_t comp_cap = 0;
-  hipEvent_t comp_ev[2] = {};
-  // per-read mate lists (mg_mates.hip, mg_build_mate_pairs): one CSR of mg_mate
-  // records over the reads; mates_ready until new reads arrive (reset_derived)
-  bool mates_ready = false;
-  uint64_t n_mates = 0;
-  uint64_t* d_mate_start = nullptr;  // start[A] (n + 2)
-  size_t mate_start_cap = 0;
-  mg_mate* d_mates = nullptr;
-  size_t mates_cap = 0;
-  hipEvent_t mate_ev[2] = {};
-  // contig strings (mg_contigs.hip, mg_build_contigs): one descriptor and one
-  // output position per piece, the edges' string starts and the ASCII bases;
-  // contigs_ready until new reads arrive (reset_derived)
-  bool contigs_ready = false;
-  uint64_t n_contig_edges = 0, n_contig_bases = 0;
-  uint64_t* d_ctg_desc = nullptr;  // per piece: slot | position << 32 | read length << 48
-  size_t ctg_desc_cap = 0;
-  uint8_t* d_ctg_flag = nullptr;   // per piece: bit 0 forward strand, bit 1 'N' first
-  size_t ctg_flag_cap = 0;
-  uint64_t* d_ctg_len = nullptr;   // per piece: bases it writes (scan input)
-  size_t ctg_len_cap = 0;
-  uint64_t* d_ctg_pos = nullptr;   // per piece (+ 1): where it writes
-  size_t ctg_pos_cap = 0;
-  uint64_t* d_ctg_pbase = nullptr; // per edge (+ 1): its first piece
-  size_t ctg_pbase_cap = 0;
-  uint64_t* d_ctg_start = nullptr; // per edge (+ 1): where its string starts
-  size_t ctg_start_cap = 0;
-  char* d_ctg_out = nullptr;
-  size_t ctg_out_cap = 0;
-  uint8_t* d_ctg_tmp = nullptr;    // the scan's temporary storage
-  size_t ctg_tmp_cap = 0;
-  unsigned long long* d_ctg_ctl = nullptr;  // [0] = first invalid piece
-  size_t ctg_ctl_cap = 0;
-  hipEvent_t ctg_ev[2] = {};
-  // read placements (mg_places.hip, mg_build_placements): one CSR of mg_place
-  // records over the reads, each read's forward-placement count, and what
-  // mg_edge_coverage reads again: the edges and, per list entry of every edge
-  // ("entry space", edge k at pl_ebase[k]), its read, edge and distance.
-  // places_ready until new reads arrive (reset_derived)
-  bool places_ready = false;
-  uint64_t n_places = 0;
-  std::vector<mg_contig_edge> pl_edges;  // the edges of the last build (messages, chunking)
-  std::vector<uint64_t> pl_ebase;        // per edge (+ 1): its first entry
-  uint64_t* d_pl_start = nullptr;  // start[A] (n + 2)
-  size_t pl_start_cap = 0;
-  mg_place* d_places = nullptr;
-  size_t places_cap = 0;
-  uint32_t* d_pl_fwd = nullptr;  // forward placements of read A (n + 2)
-  size_t pl_fwd_cap = 0;
-  mg_contig_edge* d_pl_edges = nullptr;
-  size_t pl_edges_cap = 0;
-  uint64_t* d_pl_ebase = nullptr;
-  size_t pl_ebase_cap = 0;
-  uint32_t* d_pl_eread = nullptr;
-  size_t pl_eread_cap = 0;
-  uint32_t* d_pl_eedge = nullptr;
-  size_t pl_eedge_cap = 0;
-  uint64_t* d_pl_edist = nullptr;
-  size_t pl_edist_cap = 0;
-  // option "cov_budget" (tests): per-base counters one chunk of mg_edge_coverage holds (0 = 2^25)
-  uint64_t cov_budget = 0;
   // d_freq belongs to the resident reads (set by the device ingest, cleared by an upload)
   bool freq_ready = false;
-  hipEvent_t pl_ev[2] = {};
+  // the derived stages, one struct each (above)
+  DiscStage disc;
+  CompStage comp;
+  MateStage mates;
+  ContigStage contigs;
+  PlaceStage places;
 };
 
 #define MG_TRY(expr)                                                                  \
@@ -489,6 +526,16 @@ inline hipError_t ensure(mg_ctx* ctx, T** p, size_t* cap, size_t count, const ch
   do {                                                                                          \
     if (ensure(ctx, &ctx->field, &ctx->capf, (count), #field) != hipSuccess) return -1;         \
   } while (0)
+template <typename T>
+inline hipError_t DevArray<T>::ensure(mg_ctx* ctx, size_t count, const char* what) {
+  return ::ensure(ctx, &p, &cap, count, what);
+}
+// DevArray::ensure() of a stage's array under the name its messages carry (the
+// d_* names callers know); returns -1 from the caller with ctx->err set
+#define MG_GROW(arr, count, what)                                         \
+  do {                                                                    \
+    if ((arr).ensure(ctx, (count), (what)) != hipSuccess) return -1;      \
+  } while (0)
 // a launch wrapper that failed: keep the cause a callee left in ctx->err
 inline int launch_fail(mg_ctx* ctx, const std::string& what) {
   ctx->err = ctx->err.empty() ? what : what + ": " + ctx->err;
@@ -533,11 +580,11 @@ inline void reset_derived(mg_ctx* ctx) {
   ctx->n_contained = 0;
   ctx->n_rows = 0;
   ctx->rows_found = false;
-  ctx->disc_ready = false;
-  ctx->comp_ready = false;
-  ctx->mates_ready = false;
-  ctx->contigs_ready = false;
-  ctx->places_ready = false;
+  ctx->disc.ready = false;
+  ctx->comp.ready = false;
+  ctx->mates.ready = false;
+  ctx->contigs.ready = false;
+  ctx->places.ready = false;
 }
 
 // mg_dataset.hip: the ingest's per-record stage alone (k_ingest / k_ingest_long
@@ -548,18 +595,6 @@ inline void reset_derived(mg_ctx* ctx) {
 uint32_t ingest_record_words(uint64_t longest);
 int ingest_records(mg_ctx* ctx, const char* d_ascii, const uint64_t* d_off, uint64_t n, uint32_t min_overlap,
                    uint32_t cw, uint64_t* canon, uint16_t* len, uint8_t* valid, uint8_t* fwd);
-// mg_mates.hip: frees the mate-list buffers (mg_destroy)
-void mates_release(mg_ctx* ctx);
-// mg_contigs.hip: frees the contig buffers (mg_destroy)
-void contigs_release(mg_ctx* ctx);
-// mg_places.hip: frees the placement buffers (mg_destroy)
-void places_release(mg_ctx* ctx);
-
-// mg_disc.hip: frees the discovery-list buffers (mg_destroy)
-void disc_release(mg_ctx* ctx);
-// mg_comp.hip: frees the component buffers (mg_destroy)
-void comp_release(mg_ctx* ctx);
-
 // D(A) and what is derived from it need the whole multiset in one context
 inline int whole_multiset(mg_ctx* ctx, const char* who) {
   if (ctx->nranks > 1 || ctx->read_lo || ctx->read_hi)

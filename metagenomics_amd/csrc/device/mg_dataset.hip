@@ -28,12 +28,10 @@
 #include <cstdint>
 #include <vector>
 
-#include "mg_ctx.hpp"
 #include "mg_overlap.h"
+#include "mg_stage.hpp"
 
 namespace {
-
-constexpr int kThreads = 256;
 
 // ASCII (concatenated, offsets) or 2-bit codes (fixed stride, lengths) source
 struct IngestSrc {
@@ -237,17 +235,6 @@ __global__ __launch_bounds__(kThreads) void k_dedup_freq(const uint32_t* __restr
   if (u < nu) freq[u] = (uint32_t)((u + 1 < nu ? first[u + 1] : ngood) - first[u]);
 }
 
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
-uint32_t blocks(uint64_t n) { return (uint32_t)((n + kThreads - 1) / kThreads); }
-
 template <int W>
 struct Ingest {
   // W = 0: reads longer than 1,024 bp, cw words per read (k_ingest_long)
@@ -255,41 +242,41 @@ struct Ingest {
                  uint32_t cw = 0) {
     hipStream_t st = ctx->stream;
     const uint32_t CW = W ? (uint32_t)W : cw;
-    DevBuf<uint64_t> canon, key_a, key_b;
-    DevBuf<uint16_t> len, lkey_a, lkey_b;
-    DevBuf<uint8_t> valid;
-    DevBuf<uint32_t> idx_a, idx_b, start, uid, first;
-    DevBuf<unsigned int> lr;
-    DevBuf<unsigned long long> nsel;
-    MG_TRY(canon.alloc(n * CW));
-    MG_TRY(len.alloc(n));
-    MG_TRY(valid.alloc(n));
-    MG_TRY(lr.alloc(2));
-    MG_TRY(nsel.alloc(1));
+    Scratch<uint64_t> canon, key_a, key_b;
+    Scratch<uint16_t> len, lkey_a, lkey_b;
+    Scratch<uint8_t> valid;
+    Scratch<uint32_t> idx_a, idx_b, start, uid, first;
+    Scratch<unsigned int> lr;
+    Scratch<unsigned long long> nsel;
+    MG_SCRATCH(canon, n * CW, "ingest canonical words");
+    MG_SCRATCH(len, n, "ingest read lengths");
+    MG_SCRATCH(valid, n, "ingest filter flags");
+    MG_SCRATCH(lr, 2, "ingest length range");
+    MG_SCRATCH(nsel, 1, "ingest valid count");
     const unsigned int lr0[2] = {0xFFFFFFFFu, 0u};
     MG_TRY(hipMemcpyAsync(lr.p, lr0, sizeof(lr0), hipMemcpyHostToDevice, st));
     if (n) {
       if (W == 0 && ascii)
-        hipLaunchKernelGGL((k_ingest_long<true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, CW,
+        hipLaunchKernelGGL((k_ingest_long<true>), dim3(blocks_for(n)), dim3(kThreads), 0, st, s, n, min_overlap, CW,
                            canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       else if (W == 0)
-        hipLaunchKernelGGL((k_ingest_long<false>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, CW,
+        hipLaunchKernelGGL((k_ingest_long<false>), dim3(blocks_for(n)), dim3(kThreads), 0, st, s, n, min_overlap, CW,
                            canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       else if (ascii)
-        hipLaunchKernelGGL((k_ingest<(W ? W : 1), true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap,
+        hipLaunchKernelGGL((k_ingest<(W ? W : 1), true>), dim3(blocks_for(n)), dim3(kThreads), 0, st, s, n, min_overlap,
                            canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       else
-        hipLaunchKernelGGL((k_ingest<(W ? W : 1), false>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap,
+        hipLaunchKernelGGL((k_ingest<(W ? W : 1), false>), dim3(blocks_for(n)), dim3(kThreads), 0, st, s, n, min_overlap,
                            canon.p, len.p, valid.p, lr.p, (uint8_t*)nullptr);
       MG_TRY(hipGetLastError());
     }
     // indices of the valid reads, in input order
-    MG_TRY(idx_a.alloc(n));
-    MG_TRY(idx_b.alloc(n));
+    MG_SCRATCH(idx_a, n, "ingest sort values");
+    MG_SCRATCH(idx_b, n, "ingest sort values");
     size_t tb = 0;
     hipcub::CountingInputIterator<uint32_t> it(0);
     MG_TRY(hipcub::DeviceSelect::Flagged(nullptr, tb, it, valid.p, idx_a.p, nsel.p, (int)n, st));
-    DevBuf<uint8_t> tmp;
+    Scratch<uint8_t> tmp;
     size_t tmp_bytes = tb;
     {
       size_t t2 = 0;
@@ -300,7 +287,7 @@ struct Ingest {
       MG_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, t2, start.p, uid.p, (int)n, st));
       tmp_bytes = std::max(tmp_bytes, t2);
     }
-    MG_TRY(tmp.alloc(tmp_bytes));
+    MG_SCRATCH(tmp, tmp_bytes, "ingest select, sort and scan storage");
     tb = tmp_bytes;
     MG_TRY(hipcub::DeviceSelect::Flagged(tmp.p, tb, it, valid.p, idx_a.p, nsel.p, (int)n, st));
     unsigned long long ng = 0;
@@ -310,23 +297,23 @@ struct Ingest {
     MG_TRY(hipStreamSynchronize(st));
     const uint64_t ngood = ng;
     // LSD: length, then words W-1 .. 0 (stable) = (words, length) order
-    MG_TRY(key_a.alloc(ngood));
-    MG_TRY(key_b.alloc(ngood));
-    MG_TRY(lkey_a.alloc(ngood));
-    MG_TRY(lkey_b.alloc(ngood));
+    MG_SCRATCH(key_a, ngood, "ingest word keys");
+    MG_SCRATCH(key_b, ngood, "ingest word keys");
+    MG_SCRATCH(lkey_a, ngood, "ingest length keys");
+    MG_SCRATCH(lkey_b, ngood, "ingest length keys");
     uint32_t* cur = idx_a.p;
     uint32_t* alt = idx_b.p;
     if (ngood) {
       const bool lens_differ = lrh[0] != lrh[1];
       if (lens_differ) {
-        hipLaunchKernelGGL(k_gather_len, dim3(blocks(ngood)), dim3(kThreads), 0, st, len.p, cur, ngood, lkey_a.p);
+        hipLaunchKernelGGL(k_gather_len, dim3(blocks_for(ngood)), dim3(kThreads), 0, st, len.p, cur, ngood, lkey_a.p);
         tb = tmp_bytes;
         MG_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, lkey_a.p, lkey_b.p, cur, alt, (int)ngood, 0, 16, st));
         std::swap(cur, alt);
       }
       const uint32_t wused = (lrh[1] + 31) / 32;  // words past the longest read are all zero
       for (int k = (int)wused - 1; k >= 0; --k) {
-        hipLaunchKernelGGL((k_gather_word<W>), dim3(blocks(ngood)), dim3(kThreads), 0, st, canon.p, cur, ngood, k,
+        hipLaunchKernelGGL((k_gather_word<W>), dim3(blocks_for(ngood)), dim3(kThreads), 0, st, canon.p, cur, ngood, k,
                            key_a.p, CW);
         tb = tmp_bytes;
         MG_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, key_a.p, key_b.p, cur, alt, (int)ngood, 0, 64, st));
@@ -334,10 +321,10 @@ struct Ingest {
       }
     }
     // dedup + IDs + frequency
-    MG_TRY(start.alloc(ngood));
-    MG_TRY(uid.alloc(ngood));
+    MG_SCRATCH(start, ngood, "ingest run starts");
+    MG_SCRATCH(uid, ngood, "ingest unique IDs");
     if (ngood) {
-      hipLaunchKernelGGL((k_dedup_flags<W>), dim3(blocks(ngood)), dim3(kThreads), 0, st, canon.p, len.p, cur, ngood,
+      hipLaunchKernelGGL((k_dedup_flags<W>), dim3(blocks_for(ngood)), dim3(kThreads), 0, st, canon.p, len.p, cur, ngood,
                          start.p, CW);
       tb = tmp_bytes;
       MG_TRY(hipcub::DeviceScan::ExclusiveSum(tmp.p, tb, start.p, uid.p, (int)ngood, st));
@@ -359,11 +346,11 @@ struct Ingest {
     MG_ENSURE(d_len, len_cap, nu + 1);
     MG_ENSURE(d_freq, freq_cap, nu + 1);
     MG_TRY(hipMemsetAsync(ctx->d_words, 0, nw * sizeof(uint64_t), st));
-    MG_TRY(first.alloc(nu));
+    MG_SCRATCH(first, nu, "ingest run firsts");
     if (ngood) {
-      hipLaunchKernelGGL((k_dedup_write<W>), dim3(blocks(ngood)), dim3(kThreads), 0, st, canon.p, len.p, cur, start.p,
+      hipLaunchKernelGGL((k_dedup_write<W>), dim3(blocks_for(ngood)), dim3(kThreads), 0, st, canon.p, len.p, cur, start.p,
                          uid.p, ngood, ctx->maxw, ctx->stride, ctx->d_words, ctx->d_len, first.p, CW);
-      hipLaunchKernelGGL(k_dedup_freq, dim3(blocks(nu)), dim3(kThreads), 0, st, first.p, nu, ngood, ctx->d_freq);
+      hipLaunchKernelGGL(k_dedup_freq, dim3(blocks_for(nu)), dim3(kThreads), 0, st, first.p, nu, ngood, ctx->d_freq);
       MG_TRY(hipGetLastError());
     }
     MG_TRY(hipStreamSynchronize(st));
@@ -401,7 +388,7 @@ int ingest(mg_ctx* ctx, const IngestSrc& s, bool ascii, uint64_t n, uint64_t max
 template <int W>
 void launch_records(hipStream_t st, const IngestSrc& s, uint64_t n, uint32_t min_overlap, uint64_t* canon,
                     uint16_t* len, uint8_t* valid, unsigned int* lr, uint8_t* fwd) {
-  hipLaunchKernelGGL((k_ingest<W, true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, canon, len, valid,
+  hipLaunchKernelGGL((k_ingest<W, true>), dim3(blocks_for(n)), dim3(kThreads), 0, st, s, n, min_overlap, canon, len, valid,
                      lr, fwd);
 }
 
@@ -416,8 +403,8 @@ int ingest_records(mg_ctx* ctx, const char* d_ascii, const uint64_t* d_off, uint
                    uint32_t cw, uint64_t* canon, uint16_t* len, uint8_t* valid, uint8_t* fwd) {
   if (!n) return 0;
   hipStream_t st = ctx->stream;
-  DevBuf<unsigned int> lr;  // the kernels' length range: not used here
-  MG_TRY(lr.alloc(2));
+  Scratch<unsigned int> lr;  // the kernels' length range: not used here
+  MG_SCRATCH(lr, 2, "record length range");
   MG_TRY(hipMemsetAsync(lr.p, 0, 2 * sizeof(unsigned int), st));
   const IngestSrc s{d_ascii, d_off, nullptr, 0, nullptr};
   switch (cw) {
@@ -433,7 +420,7 @@ int ingest_records(mg_ctx* ctx, const char* d_ascii, const uint64_t* d_off, uint
     case 32: launch_records<32>(st, s, n, min_overlap, canon, len, valid, lr.p, fwd); break;
     default:
       if (cw < 33) return set_err(ctx, "unsupported record width");
-      hipLaunchKernelGGL((k_ingest_long<true>), dim3(blocks(n)), dim3(kThreads), 0, st, s, n, min_overlap, cw, canon,
+      hipLaunchKernelGGL((k_ingest_long<true>), dim3(blocks_for(n)), dim3(kThreads), 0, st, s, n, min_overlap, cw, canon,
                          len, valid, lr.p, fwd);
   }
   MG_TRY(hipGetLastError());
@@ -454,10 +441,10 @@ int mg_ingest_ascii(mg_ctx* ctx, const char* concat, const uint64_t* offsets, ui
     if (L > min_overlap && L <= 65535) longest_valid_len = std::max(longest_valid_len, L);
   }
   const uint64_t total = n_raw ? offsets[n_raw] : 0;
-  DevBuf<char> d_ascii;
-  DevBuf<uint64_t> d_off;
-  MG_TRY(d_ascii.alloc(total));
-  MG_TRY(d_off.alloc(n_raw + 1));
+  Scratch<char> d_ascii;
+  Scratch<uint64_t> d_off;
+  MG_SCRATCH(d_ascii, total, "ingest records");
+  MG_SCRATCH(d_off, n_raw + 1, "ingest record offsets");
   MG_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
   if (total) MG_TRY(hipMemcpyAsync(d_ascii.p, concat, total, hipMemcpyHostToDevice, ctx->stream));
   MG_TRY(hipMemcpyAsync(d_off.p, offsets, (n_raw + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
@@ -486,10 +473,10 @@ int mg_ingest_codes(mg_ctx* ctx, const uint8_t* codes, uint64_t n_raw, uint64_t 
     if (lens[i] > min_overlap) longest_valid_len = std::max<uint64_t>(longest_valid_len, lens[i]);
   }
   if (maxlen > stride && n_raw > 1) return set_err(ctx, "read length exceeds the row stride");
-  DevBuf<uint8_t> d_codes;
-  DevBuf<uint16_t> d_lens;
-  MG_TRY(d_codes.alloc(n_raw * stride));
-  MG_TRY(d_lens.alloc(n_raw));
+  Scratch<uint8_t> d_codes;
+  Scratch<uint16_t> d_lens;
+  MG_SCRATCH(d_codes, n_raw * stride, "ingest base codes");
+  MG_SCRATCH(d_lens, n_raw, "ingest record lengths");
   MG_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
   if (n_raw) {
     MG_TRY(hipMemcpyAsync(d_codes.p, codes, n_raw * stride, hipMemcpyHostToDevice, ctx->stream));

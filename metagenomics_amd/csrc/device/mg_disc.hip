@@ -35,13 +35,11 @@
 #include <cstring>
 #include <string>
 
-#include "mg_ctx.hpp"
 #include "mg_overlap.h"
+#include "mg_stage.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
 constexpr int kWaveReads = 32;         // consecutive reads one wavefront of k_disc_wave takes
 constexpr uint32_t kBlockCap = 2048;   // keys a workgroup sorts in LDS (16 KiB: 8 workgroups = 32 waves per CU in 128 of 160 KiB)
 constexpr uint64_t kKeyMask = (1ULL << 50) - 1;
@@ -324,87 +322,79 @@ __global__ __launch_bounds__(kThreads) void k_disc_restart(const uint64_t* __res
   out[i] = s < n_rows ? (uint64_t)pre[s] : n_disc;
 }
 
-inline uint32_t blocks_for(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, (items + kThreads - 1) / kThreads); }
-
-int read_ctl(mg_ctx* ctx, unsigned long long* host) {
-  MG_TRY(hipMemcpyAsync(host, ctx->d_disc_ctl, kDiscCtl * sizeof(unsigned long long), hipMemcpyDeviceToHost,
-                        ctx->stream));
-  MG_TRY(hipStreamSynchronize(ctx->stream));
-  return 0;
-}
-
 int group_rows(mg_ctx* ctx) {
   const uint64_t N = ctx->n, R = ctx->n_rows, entries = N + 2;
   const uint32_t h = ctx->h;
-  const uint32_t block_cap = std::max<uint32_t>(kWave, std::min<uint32_t>(ctx->disc_block_cap ? ctx->disc_block_cap : kBlockCap, kBlockCap));
-  MG_ENSURE(d_disc_ctl, disc_ctl_cap, kDiscCtl);
-  MG_ENSURE(d_disc_start, disc_start_cap, entries);
-  MG_ENSURE(d_disc_cnt, disc_cnt_cap, entries);
-  MG_ENSURE(d_disc, disc_cap, R);
-  ctx->n_disc = 0;
+  const uint32_t block_cap = std::max<uint32_t>(kWave, std::min<uint32_t>(ctx->disc.block_cap ? ctx->disc.block_cap : kBlockCap, kBlockCap));
+  DiscStage& ds = ctx->disc;
+  MG_GROW(ds.ctl, kDiscCtl, "d_disc_ctl");
+  MG_GROW(ds.start, entries, "d_disc_start");
+  MG_GROW(ds.cnt, entries, "d_disc_cnt");
+  MG_GROW(ds.recs, R, "d_disc");
+  ds.n = 0;
   if (!R || !N || !ctx->nreg) {
-    MG_TRY(hipMemsetAsync(ctx->d_disc_start, 0, entries * sizeof(uint64_t), ctx->stream));
+    MG_TRY(hipMemsetAsync(ds.start.p, 0, entries * sizeof(uint64_t), ctx->stream));
     return 0;
   }
   const uint64_t list_n = std::min<uint64_t>(N, R / (kWave + 1)) + 1;
-  MG_ENSURE(d_disc_list, disc_list_cap, list_n);
-  MG_ENSURE(d_disc_boff, disc_boff_cap, list_n + 1);
+  MG_GROW(ds.list, list_n, "d_disc_list");
+  MG_GROW(ds.boff, list_n + 1, "d_disc_boff");
   size_t tb = 0;
-  MG_TRY(rocprim::exclusive_scan(nullptr, tb, ctx->d_disc_cnt, ctx->d_disc_start, (uint64_t)0, (size_t)entries,
+  MG_TRY(rocprim::exclusive_scan(nullptr, tb, ds.cnt.p, ds.start.p, (uint64_t)0, (size_t)entries,
                                  rocprim::plus<uint64_t>(), ctx->stream));
-  MG_ENSURE(d_disc_tmp, disc_tmp_cap, tb);
-  tb = ctx->disc_tmp_cap;
+  MG_GROW(ds.tmp, tb, "d_disc_tmp");
+  tb = ds.tmp.cap;
 
   const uint64_t reg_cap = ctx->rows_cap / ctx->nreg;
   const uint32_t walk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(ctx->nreg, (uint64_t)ctx->n_cu * 32));
-  MG_TRY(hipMemsetAsync(ctx->d_disc_ctl, 0, kDiscCtl * sizeof(unsigned long long), ctx->stream));
-  MG_TRY(hipMemsetAsync(ctx->d_disc_cnt, 0, entries * sizeof(uint32_t), ctx->stream));
+  MG_TRY(ctl_fill(ctx->stream, ds.ctl.p, kDiscCtl, 0));
+  MG_TRY(hipMemsetAsync(ds.cnt.p, 0, entries * sizeof(uint32_t), ctx->stream));
   hipLaunchKernelGGL(k_disc_count, dim3(walk), dim3(kThreads), 0, ctx->stream, ctx->d_rows, reg_cap, ctx->d_seg,
-                     ctx->nreg, (uint32_t)N, ctx->d_disc_cnt, ctx->d_disc_ctl);
+                     ctx->nreg, (uint32_t)N, ds.cnt.p, ds.ctl.p);
   MG_TRY(hipGetLastError());
-  MG_TRY(rocprim::exclusive_scan(ctx->d_disc_tmp, tb, ctx->d_disc_cnt, ctx->d_disc_start, (uint64_t)0,
+  MG_TRY(rocprim::exclusive_scan(ds.tmp.p, tb, ds.cnt.p, ds.start.p, (uint64_t)0,
                                  (size_t)entries, rocprim::plus<uint64_t>(), ctx->stream));
-  MG_TRY(hipMemsetAsync(ctx->d_disc_cnt, 0, entries * sizeof(uint32_t), ctx->stream));
+  MG_TRY(hipMemsetAsync(ds.cnt.p, 0, entries * sizeof(uint32_t), ctx->stream));
   hipLaunchKernelGGL(k_disc_scatter, dim3(walk), dim3(kThreads), 0, ctx->stream, ctx->d_rows, reg_cap, ctx->d_seg,
-                     ctx->nreg, (uint32_t)N, h, ctx->d_len, ctx->d_phys, ctx->d_disc_start, ctx->d_disc_cnt,
-                     ctx->d_disc, ctx->d_disc_ctl);
+                     ctx->nreg, (uint32_t)N, h, ctx->d_len, ctx->d_phys, ds.start.p, ds.cnt.p,
+                     ds.recs.p, ds.ctl.p);
   MG_TRY(hipGetLastError());
-  hipLaunchKernelGGL(k_disc_classify, dim3(blocks_for(N)), dim3(kThreads), 0, ctx->stream, ctx->d_disc_start,
-                     (uint32_t)N, block_cap, ctx->d_disc_list, list_n, ctx->d_disc_boff, ctx->d_disc_ctl);
+  hipLaunchKernelGGL(k_disc_classify, dim3(blocks_for(N)), dim3(kThreads), 0, ctx->stream, ds.start.p,
+                     (uint32_t)N, block_cap, ds.list.p, list_n, ds.boff.p, ds.ctl.p);
   MG_TRY(hipGetLastError());
   const uint64_t waves = (N + kWaveReads - 1) / kWaveReads;
-  hipLaunchKernelGGL(k_disc_wave, dim3(blocks_for(waves * kWave)), dim3(kThreads), 0, ctx->stream, ctx->d_disc,
-                     ctx->d_disc_start, (uint32_t)N, h, ctx->d_len, ctx->d_phys, ctx->d_disc_ctl);
+  hipLaunchKernelGGL(k_disc_wave, dim3(blocks_for(waves * kWave)), dim3(kThreads), 0, ctx->stream, ds.recs.p,
+                     ds.start.p, (uint32_t)N, h, ctx->d_len, ctx->d_phys, ds.ctl.p);
   MG_TRY(hipGetLastError());
   const uint32_t per_read_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(list_n, (uint64_t)ctx->n_cu * 8));
-  hipLaunchKernelGGL(k_disc_block, dim3(per_read_grid), dim3(kThreads), 0, ctx->stream, ctx->d_disc,
-                     ctx->d_disc_start, ctx->d_disc_list, list_n, h, ctx->d_len, ctx->d_phys, ctx->d_disc_ctl);
+  hipLaunchKernelGGL(k_disc_block, dim3(per_read_grid), dim3(kThreads), 0, ctx->stream, ds.recs.p,
+                     ds.start.p, ds.list.p, list_n, h, ctx->d_len, ctx->d_phys, ds.ctl.p);
   MG_TRY(hipGetLastError());
   // the class counts (and, so far, the error bits) after everything above is queued
   unsigned long long ctl[kDiscCtl];
-  if (read_ctl(ctx, ctl)) return -1;
+  MG_TRY(ctl_read(ctx->stream, ds.ctl.p, kDiscCtl, ctl));
   const uint64_t n_big = ctl[kBig] >> 32, big_total = ctl[kBig] & 0xFFFFFFFFULL;
   if (n_big && !(ctl[kErr] & kErrId)) {
-    MG_ENSURE(d_disc_big[0], disc_big_cap[0], big_total);
-    MG_ENSURE(d_disc_big[1], disc_big_cap[1], big_total);
+    MG_GROW(ds.big[0], big_total, "d_disc_big[0]");
+    MG_GROW(ds.big[1], big_total, "d_disc_big[1]");
     size_t sb = 0;
-    MG_TRY(rocprim::segmented_radix_sort_keys(nullptr, sb, ctx->d_disc_big[0], ctx->d_disc_big[1],
-                                              (unsigned int)big_total, (unsigned int)n_big, ctx->d_disc_boff,
-                                              ctx->d_disc_boff + 1, 0u, 50u, ctx->stream));
-    MG_ENSURE(d_disc_tmp, disc_tmp_cap, sb);
-    sb = ctx->disc_tmp_cap;
+    MG_TRY(rocprim::segmented_radix_sort_keys(nullptr, sb, ds.big[0].p, ds.big[1].p,
+                                              (unsigned int)big_total, (unsigned int)n_big, ds.boff.p,
+                                              ds.boff.p + 1, 0u, 50u, ctx->stream));
+    MG_GROW(ds.tmp, sb, "d_disc_tmp");
+    sb = ds.tmp.cap;
     const uint32_t g = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(n_big, (uint64_t)ctx->n_cu * 8));
-    hipLaunchKernelGGL(k_disc_gather, dim3(g), dim3(kThreads), 0, ctx->stream, ctx->d_disc, ctx->d_disc_start,
-                       ctx->d_disc_list, list_n, ctx->d_disc_boff, n_big, ctx->d_disc_big[0]);
+    hipLaunchKernelGGL(k_disc_gather, dim3(g), dim3(kThreads), 0, ctx->stream, ds.recs.p, ds.start.p,
+                       ds.list.p, list_n, ds.boff.p, n_big, ds.big[0].p);
     MG_TRY(hipGetLastError());
-    MG_TRY(rocprim::segmented_radix_sort_keys(ctx->d_disc_tmp, sb, ctx->d_disc_big[0], ctx->d_disc_big[1],
-                                              (unsigned int)big_total, (unsigned int)n_big, ctx->d_disc_boff,
-                                              ctx->d_disc_boff + 1, 0u, 50u, ctx->stream));
-    hipLaunchKernelGGL(k_disc_big_records, dim3(g), dim3(kThreads), 0, ctx->stream, ctx->d_disc, ctx->d_disc_start,
-                       ctx->d_disc_list, list_n, ctx->d_disc_boff, n_big, ctx->d_disc_big[1], h, ctx->d_len,
-                       ctx->d_phys, ctx->d_disc_ctl);
+    MG_TRY(rocprim::segmented_radix_sort_keys(ds.tmp.p, sb, ds.big[0].p, ds.big[1].p,
+                                              (unsigned int)big_total, (unsigned int)n_big, ds.boff.p,
+                                              ds.boff.p + 1, 0u, 50u, ctx->stream));
+    hipLaunchKernelGGL(k_disc_big_records, dim3(g), dim3(kThreads), 0, ctx->stream, ds.recs.p, ds.start.p,
+                       ds.list.p, list_n, ds.boff.p, n_big, ds.big[1].p, h, ctx->d_len,
+                       ctx->d_phys, ds.ctl.p);
     MG_TRY(hipGetLastError());
-    if (read_ctl(ctx, ctl)) return -1;
+    MG_TRY(ctl_read(ctx->stream, ds.ctl.p, kDiscCtl, ctl));
   }
   if (ctl[kErr] & kErrId) {
     ctx->err = "mg_build_discoveries: a row's src or dst is outside 1..n_reads (-1)";
@@ -419,44 +409,32 @@ int group_rows(mg_ctx* ctx) {
     return -3;
   }
   const uint64_t dups = ctl[kDup];
-  ctx->n_disc = R - dups;
+  ctx->disc.n = R - dups;
   if (dups) {  // tandem repeats only: drop the dead records, lists stay dense
-    MG_ENSURE(d_disc_pre, disc_pre_cap, R);
-    MG_ENSURE(d_disc_alt, disc_alt_cap, ctx->n_disc);
-    MG_ENSURE(d_disc_start_alt, disc_start_alt_cap, entries);
-    auto live = rocprim::make_transform_iterator(ctx->d_disc, DiscLive());
+    MG_GROW(ds.pre, R, "d_disc_pre");
+    MG_GROW(ds.recs_alt, ds.n, "d_disc_alt");
+    MG_GROW(ds.start_alt, entries, "d_disc_start_alt");
+    auto live = rocprim::make_transform_iterator(ds.recs.p, DiscLive());
     size_t cb = 0;
-    MG_TRY(rocprim::exclusive_scan(nullptr, cb, live, ctx->d_disc_pre, 0u, (size_t)R, rocprim::plus<uint32_t>(),
+    MG_TRY(rocprim::exclusive_scan(nullptr, cb, live, ds.pre.p, 0u, (size_t)R, rocprim::plus<uint32_t>(),
                                    ctx->stream));
-    MG_ENSURE(d_disc_tmp, disc_tmp_cap, cb);
-    cb = ctx->disc_tmp_cap;
-    MG_TRY(rocprim::exclusive_scan(ctx->d_disc_tmp, cb, live, ctx->d_disc_pre, 0u, (size_t)R,
+    MG_GROW(ds.tmp, cb, "d_disc_tmp");
+    cb = ds.tmp.cap;
+    MG_TRY(rocprim::exclusive_scan(ds.tmp.p, cb, live, ds.pre.p, 0u, (size_t)R,
                                    rocprim::plus<uint32_t>(), ctx->stream));
-    hipLaunchKernelGGL(k_disc_compact, dim3(blocks_for(R)), dim3(kThreads), 0, ctx->stream, ctx->d_disc,
-                       ctx->d_disc_pre, R, ctx->d_disc_alt);
+    hipLaunchKernelGGL(k_disc_compact, dim3(blocks_for(R)), dim3(kThreads), 0, ctx->stream, ds.recs.p,
+                       ds.pre.p, R, ds.recs_alt.p);
     MG_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_disc_restart, dim3(blocks_for(entries)), dim3(kThreads), 0, ctx->stream, ctx->d_disc_start,
-                       ctx->d_disc_pre, R, ctx->n_disc, entries, ctx->d_disc_start_alt);
+    hipLaunchKernelGGL(k_disc_restart, dim3(blocks_for(entries)), dim3(kThreads), 0, ctx->stream, ds.start.p,
+                       ds.pre.p, R, ctx->disc.n, entries, ds.start_alt.p);
     MG_TRY(hipGetLastError());
-    std::swap(ctx->d_disc, ctx->d_disc_alt);
-    std::swap(ctx->disc_cap, ctx->disc_alt_cap);
-    std::swap(ctx->d_disc_start, ctx->d_disc_start_alt);
-    std::swap(ctx->disc_start_cap, ctx->disc_start_alt_cap);
+    ds.recs.swap(ds.recs_alt);
+    ds.start.swap(ds.start_alt);
   }
   return 0;
 }
 
 }  // namespace
-
-void disc_release(mg_ctx* ctx) {
-  void* bufs[] = {ctx->d_disc_cnt, ctx->d_disc_start, ctx->d_disc,     ctx->d_disc_list,      ctx->d_disc_boff,
-                  ctx->d_disc_big[0], ctx->d_disc_big[1], ctx->d_disc_tmp, ctx->d_disc_ctl, ctx->d_disc_alt,
-                  ctx->d_disc_start_alt, ctx->d_disc_pre};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (auto& e : ctx->disc_ev)
-    if (e) (void)hipEventDestroy(e);
-}
 
 extern "C" {
 
@@ -466,23 +444,21 @@ int mg_build_discoveries(mg_ctx* ctx, uint64_t* n_disc, float* device_ms) {
   MG_TRY(hipSetDevice(ctx->device));
   if (n_disc) *n_disc = 0;
   if (device_ms) *device_ms = 0.f;
-  ctx->disc_ready = false;
-  ctx->comp_ready = false;
+  ctx->disc.ready = false;
+  ctx->comp.ready = false;
   if (whole_multiset(ctx, "mg_build_discoveries")) return -1;
   if (!ctx->index_ready || !ctx->rows_found)
     return set_err(ctx, "mg_build_discoveries: mg_find_overlaps must complete for the current index first");
   if (ctx->n_rows >> 32 || ctx->n >= 0xFFFFFFFFULL)
     return set_err(ctx, "mg_build_discoveries: 2^32 or more rows are not supported");
-  for (auto& e : ctx->disc_ev)
-    if (!e) MG_TRY(hipEventCreate(&e));
-  MG_TRY(hipEventRecord(ctx->disc_ev[0], ctx->stream));
+  MG_TRY(ctx->disc.ev.start(ctx->stream));
   const int rc = group_rows(ctx);
   if (rc) return rc;
-  MG_TRY(hipEventRecord(ctx->disc_ev[1], ctx->stream));
-  MG_TRY(hipEventSynchronize(ctx->disc_ev[1]));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->disc_ev[0], ctx->disc_ev[1]));
-  ctx->disc_ready = true;
-  if (n_disc) *n_disc = ctx->n_disc;
+  MG_TRY(ctx->disc.ev.end(ctx->stream));
+  MG_TRY(ctx->disc.ev.wait());
+  MG_TRY(ctx->disc.ev.elapsed(device_ms));
+  ctx->disc.ready = true;
+  if (n_disc) *n_disc = ctx->disc.n;
   return 0;
 }
 
@@ -492,16 +468,9 @@ int mg_copy_discoveries(mg_ctx* ctx, uint64_t* start, mg_disc* disc, uint64_t ca
   MG_TRY(hipSetDevice(ctx->device));
   if (n_copied) *n_copied = 0;
   if (whole_multiset(ctx, "mg_copy_discoveries")) return -1;
-  if (!ctx->index_ready || !ctx->rows_found || !ctx->disc_ready)
+  if (!ctx->index_ready || !ctx->rows_found || !ctx->disc.ready)
     return set_err(ctx, "mg_copy_discoveries: mg_build_discoveries must run for the current rows first");
-  if (start)
-    MG_TRY(hipMemcpyAsync(start, ctx->d_disc_start, (ctx->n + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-  const uint64_t c = disc ? std::min(cap, ctx->n_disc) : 0;
-  if (c) MG_TRY(hipMemcpyAsync(disc, ctx->d_disc, c * sizeof(mg_disc), hipMemcpyDeviceToHost, ctx->stream));
-  MG_TRY(hipStreamSynchronize(ctx->stream));
-  if (n_copied) *n_copied = c;
-  return 0;
+  return copy_csr(ctx, ctx->disc.start.p, ctx->n + 2, start, ctx->disc.recs.p, ctx->disc.n, disc, cap, n_copied);
 }
 
 }  // extern "C"

@@ -3999,16 +3999,11 @@ void mg_destroy(mg_ctx* ctx) {
                   ctx->d_kblk, ctx->d_rdst, ctx->d_cells_alt};
   for (void* b : bufs)
     if (b) (void)hipFree(b);
-  disc_release(ctx);
-  comp_release(ctx);
-  mates_release(ctx);
-  contigs_release(ctx);
-  places_release(ctx);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // (the derived stages' arrays and events go with it: DevArray, EventPair)
 }
 
 const char* mg_last_error(const mg_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -4226,11 +4221,11 @@ int mg_set_option(mg_ctx* ctx, const char* name, int64_t value) {
     return 0;
   }
   if (!strcmp(name, "disc_block_cap")) {  // tests: records the discovery lists' workgroup sort takes (0 = default)
-    ctx->disc_block_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
+    ctx->disc.block_cap = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 20));
     return 0;
   }
   if (!strcmp(name, "cov_budget")) {  // tests: per-base counters per chunk of mg_edge_coverage (0 = default)
-    ctx->cov_budget = (uint64_t)std::max<int64_t>(0, value);
+    ctx->places.cov_budget = (uint64_t)std::max<int64_t>(0, value);
     return 0;
   }
   if (!strcmp(name, "run_cap")) {  // tests: initial run records per scan region (0 = sized from the reads)
@@ -4315,8 +4310,8 @@ int setup_index(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k, bool cells =
   ctx->super_any = false;
   ctx->live_ready = false;
   ctx->rows_found = false;  // (the rows and the discovery lists belong to the last index)
-  ctx->disc_ready = false;
-  ctx->comp_ready = false;
+  ctx->disc.ready = false;
+  ctx->comp.ready = false;
   ctx->key0_ready = false;  // set by the fused build when it writes the o = 0 keys
   ctx->xchg = false;        // mg_xchg_begin sets it after this
   ctx->xchg_fused = false;  // (a plain build after a one-rank exchange step takes no exchange shortcut)
@@ -5280,8 +5275,8 @@ int mg_find_overlaps(mg_ctx* ctx, uint64_t* n_rows) {
                         std::min(ctx->read_lo, ctx->n);
   ctx->row_reruns = 0;
   ctx->rows_found = false;
-  ctx->disc_ready = false;
-  ctx->comp_ready = false;
+  ctx->disc.ready = false;
+  ctx->comp.ready = false;
   if (ensure_rows(ctx, nsrc)) return -1;
   MG_TRY(hipEventRecord(ctx->ev[4], ctx->stream));
   if (long_mode(ctx)) {

@@ -20,7 +20,7 @@
 //   k_mate_first    : the first of each run keeps its owner, the rest drop;
 //   stable radix by owner over the sequence order -> every list in ascending
 //                     sequence number = addMatePair's order;
-//   k_mate_write / k_mate_start : mg_mate records and the CSR starts.
+//   k_mate_write / k_csr_starts : mg_mate records and the CSR starts (mg_stage.hpp).
 #include <hip/hip_runtime.h>
 
 #include <hipcub/hipcub.hpp>
@@ -30,24 +30,12 @@
 #include <string>
 #include <vector>
 
-#include "mg_ctx.hpp"
 #include "mg_overlap.h"
+#include "mg_stage.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr uint32_t kNone = 0xFFFFFFFFu;  // owner of a record that is not kept
-
-// the resident reads
-struct ReadView {
-  const uint64_t* words;
-  const uint16_t* len;
-  const uint32_t* phys;  // slot of ID - 1, or nullptr (slots in ID order)
-  uint64_t n;
-  uint32_t maxw, stride;
-};
-
-__device__ __forceinline__ uint64_t slot_of(const ReadView& v, uint64_t idx) { return v.phys ? v.phys[idx] : idx; }
 
 // base p (0..3) of a packed string, most-significant base first
 __device__ __forceinline__ uint32_t base_at(const uint64_t* w, uint32_t p) {
@@ -230,48 +218,18 @@ __global__ __launch_bounds__(kThreads) void k_mate_write(const uint32_t* __restr
   out[i] = m;
 }
 
-// start[A] = records of owners below A (lower bound in the sorted owners)
-__global__ __launch_bounds__(kThreads) void k_mate_start(const uint32_t* __restrict__ sorted_owner, uint64_t n,
-                                                         uint64_t entries, uint64_t* __restrict__ start) {
-  const uint64_t a = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (a >= entries) return;
-  uint64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if ((uint64_t)sorted_owner[mid] < a) lo = mid + 1;
-    else hi = mid;
-  }
-  start[a] = lo;
-}
-
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(size_t n) { return hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(n, 1) * sizeof(T)); }
-};
-
-uint32_t blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + kThreads - 1) / kThreads); }
-
-ReadView view_of(const mg_ctx* ctx) {
-  return ReadView{ctx->d_words, ctx->d_len, ctx->d_phys, ctx->n, ctx->maxw, ctx->stride};
-}
-
 // the raw records on the device, filtered, packed and looked up
 struct Lookup {
-  DevBuf<char> ascii;
-  DevBuf<uint64_t> off, canon;
-  DevBuf<uint16_t> len;
-  DevBuf<uint8_t> valid, fwd, flags;
-  DevBuf<uint32_t> ids;
+  Scratch<char> ascii;
+  Scratch<uint64_t> off, canon;
+  Scratch<uint16_t> len;
+  Scratch<uint8_t> valid, fwd, flags;
+  Scratch<uint32_t> ids;
   uint32_t cw = 1;
 };
 
-// uploads the records, records ev0 after the transfers, runs the filter and the search
-int lookup(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint64_t n_raw, uint32_t min_overlap, Lookup& q,
-           hipEvent_t ev0) {
+// uploads the records, starts the stage's clock after the transfers, runs the filter and the search
+int lookup(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint64_t n_raw, uint32_t min_overlap, Lookup& q) {
   hipStream_t st = ctx->stream;
   uint64_t longest = 0;
   for (uint64_t i = 0; i < n_raw; ++i) {
@@ -281,22 +239,22 @@ int lookup(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint64_t n_
   }
   const uint64_t total = n_raw ? offsets[n_raw] : 0;
   q.cw = ingest_record_words(longest);
-  MG_TRY(q.ascii.alloc(total));
-  MG_TRY(q.off.alloc(n_raw + 1));
-  MG_TRY(q.canon.alloc(n_raw * q.cw));
-  MG_TRY(q.len.alloc(n_raw));
-  MG_TRY(q.valid.alloc(n_raw));
-  MG_TRY(q.fwd.alloc(n_raw));
-  MG_TRY(q.flags.alloc(n_raw));
-  MG_TRY(q.ids.alloc(n_raw));
+  MG_SCRATCH(q.ascii, total, "mate records");
+  MG_SCRATCH(q.off, n_raw + 1, "mate record offsets");
+  MG_SCRATCH(q.canon, n_raw * q.cw, "mate canonical words");
+  MG_SCRATCH(q.len, n_raw, "mate record lengths");
+  MG_SCRATCH(q.valid, n_raw, "mate filter flags");
+  MG_SCRATCH(q.fwd, n_raw, "mate strand flags");
+  MG_SCRATCH(q.flags, n_raw, "mate lookup flags");
+  MG_SCRATCH(q.ids, n_raw, "mate read IDs");
   if (total) MG_TRY(hipMemcpyAsync(q.ascii.p, concat, total, hipMemcpyHostToDevice, st));
   if (n_raw) MG_TRY(hipMemcpyAsync(q.off.p, offsets, (n_raw + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
   MG_TRY(hipMemsetAsync(q.fwd.p, 0, std::max<uint64_t>(n_raw, 1), st));
-  MG_TRY(hipEventRecord(ev0, st));
+  MG_TRY(ctx->mates.ev.start(st));
   if (!n_raw) return 0;
   if (ingest_records(ctx, q.ascii.p, q.off.p, n_raw, min_overlap, q.cw, q.canon.p, q.len.p, q.valid.p, q.fwd.p))
     return -1;
-  hipLaunchKernelGGL(k_find_reads, dim3(blocks(n_raw)), dim3(kThreads), 0, st, view_of(ctx), q.canon.p, q.len.p,
+  hipLaunchKernelGGL(k_find_reads, dim3(blocks_for(n_raw)), dim3(kThreads), 0, st, view_of(ctx), q.canon.p, q.len.p,
                      q.valid.p, q.fwd.p, n_raw, q.cw, q.ids.p, q.flags.p);
   MG_TRY(hipGetLastError());
   return 0;
@@ -309,13 +267,6 @@ int have_reads(mg_ctx* ctx, const char* who) {
 
 }  // namespace
 
-void mates_release(mg_ctx* ctx) {
-  if (ctx->d_mate_start) (void)hipFree(ctx->d_mate_start);
-  if (ctx->d_mates) (void)hipFree(ctx->d_mates);
-  for (auto& e : ctx->mate_ev)
-    if (e) (void)hipEventDestroy(e);
-}
-
 extern "C" {
 
 int mg_find_reads(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint64_t n_raw, uint32_t min_overlap,
@@ -327,17 +278,15 @@ int mg_find_reads(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint
   MG_TRY(hipSetDevice(ctx->device));
   if (n_raw >> 31) return set_err(ctx, "mg_find_reads: 2^31 or more records are not supported");
   if (have_reads(ctx, "mg_find_reads")) return -1;
-  for (auto& e : ctx->mate_ev)
-    if (!e) MG_TRY(hipEventCreate(&e));
   Lookup q;
-  if (lookup(ctx, concat, offsets, n_raw, min_overlap, q, ctx->mate_ev[0])) return -1;
-  MG_TRY(hipEventRecord(ctx->mate_ev[1], ctx->stream));
+  if (lookup(ctx, concat, offsets, n_raw, min_overlap, q)) return -1;
+  MG_TRY(ctx->mates.ev.end(ctx->stream));
   if (n_raw) {
     MG_TRY(hipMemcpyAsync(id_out, q.ids.p, n_raw * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
     MG_TRY(hipMemcpyAsync(flags_out, q.flags.p, n_raw, hipMemcpyDeviceToHost, ctx->stream));
   }
   MG_TRY(hipStreamSynchronize(ctx->stream));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->mate_ev[0], ctx->mate_ev[1]));
+  MG_TRY(ctx->mates.ev.elapsed(device_ms));
   return 0;
 }
 
@@ -349,7 +298,7 @@ int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets
   if (n_records) *n_records = 0;
   if (good_bad_pairs) good_bad_pairs[0] = good_bad_pairs[1] = 0;
   if (device_ms) *device_ms = 0.f;
-  ctx->mates_ready = false;
+  ctx->mates.ready = false;
   if (n_raw & 1) return set_err(ctx, "mg_build_mate_pairs: n_raw must be even (two mates per pair)");
   if (n_raw && (!concat || !offsets)) return set_err(ctx, "mg_build_mate_pairs: null argument");
   if (n_datasets > 256) return set_err(ctx, "mg_build_mate_pairs: more than 256 datasets (datasetNumber is UINT8)");
@@ -372,32 +321,30 @@ int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets
     if (!ctx->index_ready || !ctx->contained_done || !ctx->d_super)
       return set_err(ctx, "mg_build_mate_pairs: use_super needs a completed mg_mark_contained for the current reads");
   }
-  for (auto& e : ctx->mate_ev)
-    if (!e) MG_TRY(hipEventCreate(&e));
   hipStream_t st = ctx->stream;
   const uint64_t N = ctx->n, entries = N + 2;
-  MG_ENSURE(d_mate_start, mate_start_cap, entries);
-  MG_ENSURE(d_mates, mates_cap, n_raw);
-  ctx->n_mates = 0;
+  MG_GROW(ctx->mates.start, entries, "d_mate_start");
+  MG_GROW(ctx->mates.recs, n_raw, "d_mates");
+  ctx->mates.n = 0;
 
   Lookup q;
-  DevBuf<uint32_t> owner, mate, idx_a, idx_b, okey_a, okey_b;
-  DevBuf<uint16_t> od, od_sorted;
-  DevBuf<uint64_t> k64_a, k64_b, d_ds;
-  DevBuf<unsigned long long> ctl;
-  DevBuf<uint8_t> tmp;
-  MG_TRY(owner.alloc(n_raw));
-  MG_TRY(mate.alloc(n_raw));
-  MG_TRY(od.alloc(n_raw));
-  MG_TRY(idx_a.alloc(n_raw));
-  MG_TRY(idx_b.alloc(n_raw));
-  MG_TRY(okey_a.alloc(n_raw));
-  MG_TRY(okey_b.alloc(n_raw));
-  MG_TRY(od_sorted.alloc(n_raw));
-  MG_TRY(k64_a.alloc(n_raw));
-  MG_TRY(k64_b.alloc(n_raw));
-  MG_TRY(d_ds.alloc(ds_end.size()));
-  MG_TRY(ctl.alloc(2));
+  Scratch<uint32_t> owner, mate, idx_a, idx_b, okey_a, okey_b;
+  Scratch<uint16_t> od, od_sorted;
+  Scratch<uint64_t> k64_a, k64_b, d_ds;
+  Scratch<unsigned long long> ctl;
+  Scratch<uint8_t> tmp;
+  MG_SCRATCH(owner, n_raw, "mate record owners");
+  MG_SCRATCH(mate, n_raw, "mate record mates");
+  MG_SCRATCH(od, n_raw, "mate dataset and orientation keys");
+  MG_SCRATCH(idx_a, n_raw, "mate sort values");
+  MG_SCRATCH(idx_b, n_raw, "mate sort values");
+  MG_SCRATCH(okey_a, n_raw, "mate owner keys");
+  MG_SCRATCH(okey_b, n_raw, "mate owner keys");
+  MG_SCRATCH(od_sorted, n_raw, "mate dataset and orientation keys");
+  MG_SCRATCH(k64_a, n_raw, "mate pair keys");
+  MG_SCRATCH(k64_b, n_raw, "mate pair keys");
+  MG_SCRATCH(d_ds, ds_end.size(), "mate dataset ends");
+  MG_SCRATCH(ctl, 2, "mate control words");
   size_t tmp_bytes = 0;
   {
     size_t t = 0;
@@ -408,46 +355,43 @@ int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets
     MG_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, t, okey_a.p, okey_b.p, idx_b.p, idx_a.p, (int)n_raw, 0, 32, st));
     tmp_bytes = std::max(tmp_bytes, t);
   }
-  MG_TRY(tmp.alloc(tmp_bytes));
-  const unsigned long long ctl0[2] = {~0ull, 0ull};
-  MG_TRY(hipMemcpyAsync(ctl.p, ctl0, sizeof(ctl0), hipMemcpyHostToDevice, st));
+  MG_SCRATCH(tmp, tmp_bytes, "mate sort storage");
+  MG_TRY(ctl_fill(st, ctl.p, 1, ~0ull));  // the smallest raw index of a good mate without a read
+  MG_TRY(ctl_fill(st, ctl.p + 1, 1, 0));  // good pairs
   MG_TRY(hipMemcpyAsync(d_ds.p, ds_end.data(), ds_end.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st));
 
-  if (lookup(ctx, concat, offsets, n_raw, min_overlap, q, ctx->mate_ev[0])) return -1;
+  if (lookup(ctx, concat, offsets, n_raw, min_overlap, q)) return -1;
   unsigned long long ctlh[2] = {~0ull, 0ull};
   if (n_raw) {
-    hipLaunchKernelGGL(k_mate_emit, dim3(blocks(n_pairs)), dim3(kThreads), 0, st, view_of(ctx), q.canon.p, q.len.p,
+    hipLaunchKernelGGL(k_mate_emit, dim3(blocks_for(n_pairs)), dim3(kThreads), 0, st, view_of(ctx), q.canon.p, q.len.p,
                        q.valid.p, q.fwd.p, q.ids.p, n_pairs, q.cw, d_ds.p, n_datasets,
                        use_super ? (const uint32_t*)ctx->d_super : (const uint32_t*)nullptr, owner.p, mate.p, od.p,
                        ctl.p);
     MG_TRY(hipGetLastError());
     // (dataset, orient), then (owner, mate): stable, so a run of equal records is in sequence order
-    hipLaunchKernelGGL(k_mate_iota, dim3(blocks(n_raw)), dim3(kThreads), 0, st, idx_a.p, n_raw);
+    hipLaunchKernelGGL(k_mate_iota, dim3(blocks_for(n_raw)), dim3(kThreads), 0, st, idx_a.p, n_raw);
     size_t tb = tmp_bytes;
     MG_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, od.p, od_sorted.p, idx_a.p, idx_b.p, (int)n_raw, 0, 10, st));
-    hipLaunchKernelGGL(k_mate_gather64, dim3(blocks(n_raw)), dim3(kThreads), 0, st, owner.p, mate.p, idx_b.p, n_raw,
+    hipLaunchKernelGGL(k_mate_gather64, dim3(blocks_for(n_raw)), dim3(kThreads), 0, st, owner.p, mate.p, idx_b.p, n_raw,
                        k64_a.p);
     tb = tmp_bytes;
     MG_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, k64_a.p, k64_b.p, idx_b.p, idx_a.p, (int)n_raw, 0, 64, st));
-    hipLaunchKernelGGL(k_mate_first, dim3(blocks(n_raw)), dim3(kThreads), 0, st, owner.p, mate.p, od.p, idx_a.p, n_raw,
+    hipLaunchKernelGGL(k_mate_first, dim3(blocks_for(n_raw)), dim3(kThreads), 0, st, owner.p, mate.p, od.p, idx_a.p, n_raw,
                        okey_a.p);
     // kept records by owner over the sequence order
-    hipLaunchKernelGGL(k_mate_iota, dim3(blocks(n_raw)), dim3(kThreads), 0, st, idx_b.p, n_raw);
+    hipLaunchKernelGGL(k_mate_iota, dim3(blocks_for(n_raw)), dim3(kThreads), 0, st, idx_b.p, n_raw);
     tb = tmp_bytes;
     MG_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, okey_a.p, okey_b.p, idx_b.p, idx_a.p, (int)n_raw, 0, 32, st));
-    hipLaunchKernelGGL(k_mate_write, dim3(blocks(n_raw)), dim3(kThreads), 0, st, okey_b.p, idx_a.p, mate.p, od.p, n_raw,
-                       ctx->d_mates);
+    hipLaunchKernelGGL(k_mate_write, dim3(blocks_for(n_raw)), dim3(kThreads), 0, st, okey_b.p, idx_a.p, mate.p, od.p, n_raw,
+                       ctx->mates.recs.p);
     MG_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_mate_start, dim3(blocks(entries)), dim3(kThreads), 0, st, okey_b.p, n_raw, entries,
-                     ctx->d_mate_start);
-  MG_TRY(hipGetLastError());
-  MG_TRY(hipEventRecord(ctx->mate_ev[1], st));
+  MG_TRY(csr_starts(st, okey_b.p, n_raw, entries, ctx->mates.start.p));
+  MG_TRY(ctx->mates.ev.end(st));
   uint64_t total = 0;
-  MG_TRY(hipMemcpyAsync(ctlh, ctl.p, sizeof(ctlh), hipMemcpyDeviceToHost, st));
-  MG_TRY(hipMemcpyAsync(&total, ctx->d_mate_start + (entries - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-  MG_TRY(hipStreamSynchronize(st));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->mate_ev[0], ctx->mate_ev[1]));
+  MG_TRY(hipMemcpyAsync(&total, ctx->mates.start.p + (entries - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+  MG_TRY(ctl_read(st, ctl.p, 2, ctlh));
+  MG_TRY(ctx->mates.ev.elapsed(device_ms));
   if (good_bad_pairs) {
     good_bad_pairs[0] = ctlh[1];
     good_bad_pairs[1] = n_pairs - ctlh[1];
@@ -457,8 +401,8 @@ int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets
                " passes the filter but no resident read equals it (-2)";
     return -2;
   }
-  ctx->n_mates = total;
-  ctx->mates_ready = true;
+  ctx->mates.n = total;
+  ctx->mates.ready = true;
   if (n_records) *n_records = total;
   return 0;
 }
@@ -468,16 +412,9 @@ int mg_copy_mate_pairs(mg_ctx* ctx, uint64_t* start, mg_mate* out, uint64_t cap,
   ctx->err.clear();
   MG_TRY(hipSetDevice(ctx->device));
   if (n_copied) *n_copied = 0;
-  if (!ctx->mates_ready)
+  if (!ctx->mates.ready)
     return set_err(ctx, "mg_copy_mate_pairs: mg_build_mate_pairs must run for the current reads first");
-  if (start)
-    MG_TRY(hipMemcpyAsync(start, ctx->d_mate_start, (ctx->n + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost,
-                          ctx->stream));
-  const uint64_t c = out ? std::min(cap, ctx->n_mates) : 0;
-  if (c) MG_TRY(hipMemcpyAsync(out, ctx->d_mates, c * sizeof(mg_mate), hipMemcpyDeviceToHost, ctx->stream));
-  MG_TRY(hipStreamSynchronize(ctx->stream));
-  if (n_copied) *n_copied = c;
-  return 0;
+  return copy_csr(ctx, ctx->mates.start.p, ctx->n + 2, start, ctx->mates.recs.p, ctx->mates.n, out, cap, n_copied);
 }
 
 }  // extern "C"

@@ -20,7 +20,7 @@
 //   SortPairs   : stable radix sort of (read ID, entry) over the bits of N: a
 //                 read's records come out in ascending entry = (edge, position),
 //                 whatever the read's degree, so no per-read sort follows;
-//   k_pl_write  : the 16-byte records;  k_pl_start: start[A] by binary search.
+//   k_pl_write  : the 16-byte records;  k_csr_starts (mg_stage.hpp): start[A] by binary search.
 // mg_insert_sizes: thread per mate entry, the k x l loop of :1162-1175 over the
 //   two reads' records; count / sum / sum of squares reduced across the
 //   wavefront per dataset, then one 64-bit atomic per counter.
@@ -36,27 +36,15 @@
 #include <string>
 #include <vector>
 
-#include "mg_ctx.hpp"
 #include "mg_overlap.h"
+#include "mg_stage.hpp"
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kWave = 64;
 constexpr uint64_t kCovBudget = 1ull << 25;  // per-base counters per chunk (two 8-B words each)
 constexpr uint64_t kMaxOffset = 1ull << 40;  // an edge's overlapOffset mg_edge_coverage accepts
 
 typedef unsigned long long ull;
-
-struct LenView {
-  const uint16_t* len;
-  const uint32_t* phys;  // slot of ID - 1, or nullptr (slots in ID order)
-  uint64_t n;
-};
-
-__device__ __forceinline__ uint32_t len_of(const LenView& v, uint32_t id) {
-  return v.len[v.phys ? v.phys[id - 1] : id - 1];
-}
 
 // last k in [lo, hi) with base[k] <= x (base[lo] <= x)
 __device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ base, uint64_t lo, uint64_t hi, uint64_t x) {
@@ -146,20 +134,6 @@ __global__ __launch_bounds__(kThreads) void k_pl_write(uint64_t E, const uint32_
   out[s] = p;
 }
 
-// start[a] = first sorted record whose read ID is >= a
-__global__ __launch_bounds__(kThreads) void k_pl_start(const uint32_t* __restrict__ sorted_ids, uint64_t E,
-                                                       uint64_t entries, uint64_t* __restrict__ start) {
-  const uint64_t a = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (a >= entries) return;
-  uint64_t lo = 0, hi = E;
-  while (lo < hi) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if ((uint64_t)sorted_ids[mid] < a) lo = mid + 1;
-    else hi = mid;
-  }
-  start[a] = lo;
-}
-
 // Thread per mate entry: the quadruple loop of :1140-1179 for one (read1, j).
 __global__ __launch_bounds__(kThreads) void k_insert_sizes(const uint64_t* __restrict__ mstart,
                                                            const mg_mate* __restrict__ mates, uint64_t M, uint64_t N,
@@ -204,7 +178,7 @@ struct EdgeInfo {
   uint32_t pad;
 };
 
-__global__ __launch_bounds__(kThreads) void k_cov_edges(LenView v, const mg_contig_edge* __restrict__ edges,
+__global__ __launch_bounds__(kThreads) void k_cov_edges(ReadView v, const mg_contig_edge* __restrict__ edges,
                                                         uint64_t n_edges, EdgeInfo* __restrict__ info,
                                                         ull* __restrict__ ctl) {
   const uint64_t k = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
@@ -227,7 +201,7 @@ __global__ __launch_bounds__(kThreads) void k_cov_edges(LenView v, const mg_cont
 }
 
 // Thread per entry: D + len(read) <= L + 1, and the edge's frequency sum.
-__global__ __launch_bounds__(kThreads) void k_cov_entries(LenView v, uint64_t E, const uint32_t* __restrict__ eread,
+__global__ __launch_bounds__(kThreads) void k_cov_entries(ReadView v, uint64_t E, const uint32_t* __restrict__ eread,
                                                           const uint32_t* __restrict__ eedge,
                                                           const uint64_t* __restrict__ edist,
                                                           const EdgeInfo* __restrict__ info,
@@ -247,7 +221,7 @@ __global__ __launch_bounds__(kThreads) void k_cov_entries(LenView v, uint64_t E,
 }
 
 // Entries [e0, e1) of one chunk: +word at the interval's start, -word one past its end.
-__global__ __launch_bounds__(kThreads) void k_cov_delta(LenView v, uint64_t e0, uint64_t e1,
+__global__ __launch_bounds__(kThreads) void k_cov_delta(ReadView v, uint64_t e0, uint64_t e1,
                                                         const uint32_t* __restrict__ eread,
                                                         const uint32_t* __restrict__ eedge,
                                                         const uint64_t* __restrict__ edist,
@@ -287,38 +261,7 @@ __global__ __launch_bounds__(kThreads) void k_cov_reduce(const uint64_t* __restr
   wave_add_by_key<3>(k, v[0] != 0, v, out);
 }
 
-template <typename T>
-struct DevBuf {
-  T* p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-};
-#define PL_ALLOC(buf, count, what)                                                                                \
-  do {                                                                                                            \
-    if (ctx_malloc(ctx, reinterpret_cast<void**>(&(buf).p), (size_t)(count) * sizeof(*(buf).p), what) != hipSuccess) \
-      return -1;                                                                                                  \
-  } while (0)
-
-uint32_t blocks(uint64_t n) { return (uint32_t)std::max<uint64_t>(1, (n + kThreads - 1) / kThreads); }
-
-LenView view_of(const mg_ctx* ctx) { return LenView{ctx->d_len, ctx->d_phys, ctx->n}; }
-
-std::string edge_name(const mg_ctx* ctx, uint64_t k) {
-  return "edge " + std::to_string(k) + " (" + std::to_string(ctx->pl_edges[k].src) + ", " +
-         std::to_string(ctx->pl_edges[k].dst) + ")";
-}
-
 }  // namespace
-
-void places_release(mg_ctx* ctx) {
-  void* bufs[] = {ctx->d_pl_start, ctx->d_places,   ctx->d_pl_fwd,   ctx->d_pl_edges,
-                  ctx->d_pl_ebase, ctx->d_pl_eread, ctx->d_pl_eedge, ctx->d_pl_edist};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
-  for (auto& e : ctx->pl_ev)
-    if (e) (void)hipEventDestroy(e);
-}
 
 extern "C" {
 
@@ -329,50 +272,40 @@ int mg_build_placements(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edg
   ctx->err.clear();
   if (n_places) *n_places = 0;
   if (device_ms) *device_ms = 0.f;
-  ctx->places_ready = false;
+  ctx->places.ready = false;
   if ((n_edges && !edges) || (n_list && (!reads || !offs || !ors)))
     return set_err(ctx, "mg_build_placements: null argument");
   MG_TRY(hipSetDevice(ctx->device));
   if (whole_multiset(ctx, "mg_build_placements")) return -1;
   if (ctx->n && !ctx->d_len) return set_err(ctx, "mg_build_placements: no reads on the device");
   if (n_edges >> 31) return set_err(ctx, "mg_build_placements: 2^31 or more edges are not supported");
-  std::vector<uint64_t> ebase(n_edges + 1, 0);
-  for (uint64_t k = 0; k < n_edges; ++k) {
-    if (edges[k].first > n_list || edges[k].n > n_list - edges[k].first)
-      return set_err(ctx, "mg_build_placements: edge " + std::to_string(k) + " (" + std::to_string(edges[k].src) +
-                              ", " + std::to_string(edges[k].dst) + "): its list range lies outside the " +
-                              std::to_string(n_list) + " list entries");
-    ebase[k + 1] = ebase[k] + edges[k].n;
-  }
+  std::vector<uint64_t> ebase;
+  if (edge_bases(ctx, "mg_build_placements", edges, n_edges, n_list, 0, ebase)) return -1;
   const uint64_t E = ebase[n_edges], N = ctx->n, entries = N + 2;
   if (E >> 31) return set_err(ctx, "mg_build_placements: 2^31 or more list entries are not supported");
-  for (auto& e : ctx->pl_ev)
-    if (!e) MG_TRY(hipEventCreate(&e));
   hipStream_t st = ctx->stream;
-  MG_ENSURE(d_pl_start, pl_start_cap, entries);
-  MG_ENSURE(d_places, places_cap, E);
-  MG_ENSURE(d_pl_fwd, pl_fwd_cap, entries);
-  MG_ENSURE(d_pl_edges, pl_edges_cap, n_edges);
-  MG_ENSURE(d_pl_ebase, pl_ebase_cap, n_edges + 1);
-  MG_ENSURE(d_pl_eread, pl_eread_cap, E);
-  MG_ENSURE(d_pl_eedge, pl_eedge_cap, E);
-  MG_ENSURE(d_pl_edist, pl_edist_cap, E);
-  DevBuf<uint32_t> d_reads, keys_a, keys_b, vals_a, vals_b;
-  DevBuf<uint16_t> d_offs;
-  DevBuf<uint8_t> d_ors, efwd, tmp;
-  DevBuf<uint64_t> val, incl;
-  DevBuf<ull> ctl;
-  PL_ALLOC(d_reads, n_list, "placement list reads");
-  PL_ALLOC(d_offs, n_list, "placement list offsets");
-  PL_ALLOC(d_ors, n_list, "placement list orientations");
-  PL_ALLOC(efwd, E, "placement strands");
-  PL_ALLOC(val, E, "placement offsets");
-  PL_ALLOC(incl, E, "placement offset sums");
-  PL_ALLOC(keys_a, E, "placement sort keys");
-  PL_ALLOC(keys_b, E, "placement sort keys");
-  PL_ALLOC(vals_a, E, "placement sort values");
-  PL_ALLOC(vals_b, E, "placement sort values");
-  PL_ALLOC(ctl, 1, "placement control word");
+  PlaceStage& pl = ctx->places;
+  MG_GROW(pl.start, entries, "d_pl_start");
+  MG_GROW(pl.recs, E, "d_places");
+  MG_GROW(pl.fwd, entries, "d_pl_fwd");
+  MG_GROW(pl.d_edges, n_edges, "d_pl_edges");
+  MG_GROW(pl.d_ebase, n_edges + 1, "d_pl_ebase");
+  MG_GROW(pl.eread, E, "d_pl_eread");
+  MG_GROW(pl.eedge, E, "d_pl_eedge");
+  MG_GROW(pl.edist, E, "d_pl_edist");
+  EdgeLists lists;
+  Scratch<uint32_t> keys_a, keys_b, vals_a, vals_b;
+  Scratch<uint8_t> efwd, tmp;
+  Scratch<uint64_t> val, incl;
+  Scratch<ull> ctl;
+  MG_SCRATCH(efwd, E, "placement strands");
+  MG_SCRATCH(val, E, "placement offsets");
+  MG_SCRATCH(incl, E, "placement offset sums");
+  MG_SCRATCH(keys_a, E, "placement sort keys");
+  MG_SCRATCH(keys_b, E, "placement sort keys");
+  MG_SCRATCH(vals_a, E, "placement sort values");
+  MG_SCRATCH(vals_b, E, "placement sort values");
+  MG_SCRATCH(ctl, 1, "placement control word");
   int end_bit = 1;
   while (end_bit < 32 && (N >> end_bit)) ++end_bit;
   size_t scan_bytes = 0, sort_bytes = 0;
@@ -380,58 +313,49 @@ int mg_build_placements(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edg
   MG_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (int)E, 0,
                                             end_bit, st));
   const size_t tmp_bytes = std::max(scan_bytes, sort_bytes);
-  PL_ALLOC(tmp, tmp_bytes, "placement scan and sort storage");
-  if (n_edges)
-    MG_TRY(hipMemcpyAsync(ctx->d_pl_edges, edges, n_edges * sizeof(mg_contig_edge), hipMemcpyHostToDevice, st));
-  if (n_list) {
-    MG_TRY(hipMemcpyAsync(d_reads.p, reads, n_list * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    MG_TRY(hipMemcpyAsync(d_offs.p, offs, n_list * sizeof(uint16_t), hipMemcpyHostToDevice, st));
-    MG_TRY(hipMemcpyAsync(d_ors.p, ors, n_list, hipMemcpyHostToDevice, st));
-  }
-  MG_TRY(hipMemcpyAsync(ctx->d_pl_ebase, ebase.data(), (n_edges + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  const ull none = ~0ull;
-  MG_TRY(hipMemcpyAsync(ctl.p, &none, sizeof(none), hipMemcpyHostToDevice, st));
-  MG_TRY(hipMemsetAsync(ctx->d_pl_fwd, 0, entries * sizeof(uint32_t), st));
+  MG_SCRATCH(tmp, tmp_bytes, "placement scan and sort storage");
+  if (n_edges) MG_TRY(hipMemcpyAsync(pl.d_edges.p, edges, n_edges * sizeof(mg_contig_edge), hipMemcpyHostToDevice, st));
+  if (lists.upload(ctx, "placement", reads, offs, ors, n_list)) return -1;
+  MG_TRY(hipMemcpyAsync(pl.d_ebase.p, ebase.data(), (n_edges + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+  MG_TRY(ctl_fill(st, ctl.p, 1, ~0ull));
+  MG_TRY(hipMemsetAsync(pl.fwd.p, 0, entries * sizeof(uint32_t), st));
 
-  MG_TRY(hipEventRecord(ctx->pl_ev[0], st));
+  MG_TRY(pl.ev.start(st));
   if (E) {
-    hipLaunchKernelGGL(k_pl_entry, dim3(blocks(E)), dim3(kThreads), 0, st, ctx->d_pl_edges, ctx->d_pl_ebase, n_edges,
-                       d_reads.p, d_offs.p, d_ors.p, E, N, ctx->d_pl_eread, ctx->d_pl_eedge, efwd.p, val.p, ctl.p);
+    hipLaunchKernelGGL(k_pl_entry, dim3(blocks_for(E)), dim3(kThreads), 0, st, pl.d_edges.p, pl.d_ebase.p, n_edges,
+                       lists.reads.p, lists.offs.p, lists.ors.p, E, N, pl.eread.p, pl.eedge.p, efwd.p, val.p, ctl.p);
     MG_TRY(hipGetLastError());
     size_t tb = tmp_bytes;
     MG_TRY(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, val.p, incl.p, (int64_t)E, st));
   }
   // the read IDs index the forward counts from here on: the error word decides first
   ull bad = ~0ull;
-  MG_TRY(hipMemcpyAsync(&bad, ctl.p, sizeof(bad), hipMemcpyDeviceToHost, st));
-  MG_TRY(hipStreamSynchronize(st));
+  MG_TRY(ctl_read(st, ctl.p, 1, &bad));
   if (bad != ~0ull) {
     const uint64_t k = (uint64_t)(std::upper_bound(ebase.begin(), ebase.end(), (uint64_t)bad) - ebase.begin()) - 1;
-    ctx->err = "mg_build_placements: edge " + std::to_string(k) + " (" + std::to_string(edges[k].src) + ", " +
-               std::to_string(edges[k].dst) + "), list entry " + std::to_string(bad - ebase[k]) + ": read ID " +
+    ctx->err = "mg_build_placements: " + edge_name(edges, k) + ", list entry " + std::to_string(bad - ebase[k]) + ": read ID " +
                std::to_string(reads[edges[k].first + (bad - ebase[k])]) + " outside 1.." + std::to_string(N) + " (-2)";
     return -2;
   }
   if (E) {
-    hipLaunchKernelGGL(k_pl_dist, dim3(blocks(E)), dim3(kThreads), 0, st, E, ctx->d_pl_eedge, ctx->d_pl_ebase, incl.p,
-                       ctx->d_pl_eread, efwd.p, ctx->d_pl_edist, keys_a.p, vals_a.p, ctx->d_pl_fwd);
+    hipLaunchKernelGGL(k_pl_dist, dim3(blocks_for(E)), dim3(kThreads), 0, st, E, pl.eedge.p, pl.d_ebase.p, incl.p,
+                       pl.eread.p, efwd.p, pl.edist.p, keys_a.p, vals_a.p, pl.fwd.p);
     MG_TRY(hipGetLastError());
     size_t tb = tmp_bytes;
     MG_TRY(hipcub::DeviceRadixSort::SortPairs(tmp.p, tb, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (int)E, 0, end_bit,
                                               st));
-    hipLaunchKernelGGL(k_pl_write, dim3(blocks(E)), dim3(kThreads), 0, st, E, vals_b.p, ctx->d_pl_eedge, efwd.p,
-                       ctx->d_pl_edist, ctx->d_places);
+    hipLaunchKernelGGL(k_pl_write, dim3(blocks_for(E)), dim3(kThreads), 0, st, E, vals_b.p, pl.eedge.p, efwd.p,
+                       pl.edist.p, pl.recs.p);
     MG_TRY(hipGetLastError());
   }
-  hipLaunchKernelGGL(k_pl_start, dim3(blocks(entries)), dim3(kThreads), 0, st, keys_b.p, E, entries, ctx->d_pl_start);
-  MG_TRY(hipGetLastError());
-  MG_TRY(hipEventRecord(ctx->pl_ev[1], st));
+  MG_TRY(csr_starts(st, keys_b.p, E, entries, pl.start.p));
+  MG_TRY(pl.ev.end(st));
   MG_TRY(hipStreamSynchronize(st));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->pl_ev[0], ctx->pl_ev[1]));
-  ctx->pl_edges.assign(edges, edges + n_edges);
-  ctx->pl_ebase.swap(ebase);
-  ctx->n_places = E;
-  ctx->places_ready = true;
+  MG_TRY(pl.ev.elapsed(device_ms));
+  pl.edges.assign(edges, edges + n_edges);
+  pl.ebase.swap(ebase);
+  pl.n = E;
+  ctx->places.ready = true;
   if (n_places) *n_places = E;
   return 0;
 }
@@ -441,15 +365,9 @@ int mg_copy_placements(mg_ctx* ctx, uint64_t* start, mg_place* out, uint64_t cap
   ctx->err.clear();
   MG_TRY(hipSetDevice(ctx->device));
   if (n_copied) *n_copied = 0;
-  if (!ctx->places_ready)
+  if (!ctx->places.ready)
     return set_err(ctx, "mg_copy_placements: mg_build_placements must succeed for the current reads first");
-  if (start)
-    MG_TRY(hipMemcpyAsync(start, ctx->d_pl_start, (ctx->n + 2) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  const uint64_t c = out ? std::min(cap, ctx->n_places) : 0;
-  if (c) MG_TRY(hipMemcpyAsync(out, ctx->d_places, c * sizeof(mg_place), hipMemcpyDeviceToHost, ctx->stream));
-  MG_TRY(hipStreamSynchronize(ctx->stream));
-  if (n_copied) *n_copied = c;
-  return 0;
+  return copy_csr(ctx, ctx->places.start.p, ctx->n + 2, start, ctx->places.recs.p, ctx->places.n, out, cap, n_copied);
 }
 
 int mg_insert_sizes(mg_ctx* ctx, const uint64_t* mate_start, const mg_mate* mates, uint32_t n_datasets,
@@ -461,50 +379,48 @@ int mg_insert_sizes(mg_ctx* ctx, const uint64_t* mate_start, const mg_mate* mate
   if (n_datasets && !sums) return set_err(ctx, "mg_insert_sizes: null argument");
   for (uint32_t i = 0; i < 3 * n_datasets; ++i) sums[i] = 0;
   MG_TRY(hipSetDevice(ctx->device));
-  if (!ctx->places_ready)
+  if (!ctx->places.ready)
     return set_err(ctx, "mg_insert_sizes: mg_build_placements must succeed for the current reads first");
   const uint64_t N = ctx->n, entries = N + 2;
   hipStream_t st = ctx->stream;
-  DevBuf<uint64_t> d_ms;
-  DevBuf<mg_mate> d_m;
-  DevBuf<ull> d_sums, ctl;
-  const uint64_t* ms = ctx->d_mate_start;
-  const mg_mate* mm = ctx->d_mates;
-  uint64_t M = ctx->n_mates;
+  Scratch<uint64_t> d_ms;
+  Scratch<mg_mate> d_m;
+  Scratch<ull> d_sums, ctl;
+  const uint64_t* ms = ctx->mates.start.p;
+  const mg_mate* mm = ctx->mates.recs.p;
+  uint64_t M = ctx->mates.n;
   if (mate_start) {
     if (mate_start[0] != 0) return set_err(ctx, "mg_insert_sizes: mate_start[0] must be 0");
     for (uint64_t a = 0; a + 1 < entries; ++a)
       if (mate_start[a + 1] < mate_start[a]) return set_err(ctx, "mg_insert_sizes: mate_start must not decrease");
     M = mate_start[entries - 1];
     if (M && !mates) return set_err(ctx, "mg_insert_sizes: null argument");
-    PL_ALLOC(d_ms, entries, "caller's mate list starts");
-    PL_ALLOC(d_m, M, "caller's mate lists");
+    MG_SCRATCH(d_ms, entries, "caller's mate list starts");
+    MG_SCRATCH(d_m, M, "caller's mate lists");
     MG_TRY(hipMemcpyAsync(d_ms.p, mate_start, entries * sizeof(uint64_t), hipMemcpyHostToDevice, st));
     if (M) MG_TRY(hipMemcpyAsync(d_m.p, mates, M * sizeof(mg_mate), hipMemcpyHostToDevice, st));
     ms = d_ms.p;
     mm = d_m.p;
-  } else if (!ctx->mates_ready) {
+  } else if (!ctx->mates.ready) {
     return set_err(ctx, "mg_insert_sizes: no resident mate lists: mg_build_mate_pairs must run for the current reads "
                         "first, or pass a CSR");
   }
-  PL_ALLOC(d_sums, 3 * (uint64_t)std::max<uint32_t>(n_datasets, 1), "insert-size sums");
-  PL_ALLOC(ctl, 1, "insert-size control word");
+  MG_SCRATCH(d_sums, 3 * (uint64_t)std::max<uint32_t>(n_datasets, 1), "insert-size sums");
+  MG_SCRATCH(ctl, 1, "insert-size control word");
   MG_TRY(hipMemsetAsync(d_sums.p, 0, 3 * (size_t)std::max<uint32_t>(n_datasets, 1) * sizeof(ull), st));
-  const ull none = ~0ull;
-  MG_TRY(hipMemcpyAsync(ctl.p, &none, sizeof(none), hipMemcpyHostToDevice, st));
-  MG_TRY(hipEventRecord(ctx->pl_ev[0], st));
+  MG_TRY(ctl_fill(st, ctl.p, 1, ~0ull));
+  MG_TRY(ctx->places.ev.start(st));
   if (M) {
-    hipLaunchKernelGGL(k_insert_sizes, dim3(blocks(M)), dim3(kThreads), 0, st, ms, mm, M, N, n_datasets, max_distance,
-                       ctx->d_pl_start, ctx->d_places, d_sums.p, ctl.p);
+    hipLaunchKernelGGL(k_insert_sizes, dim3(blocks_for(M)), dim3(kThreads), 0, st, ms, mm, M, N, n_datasets, max_distance,
+                       ctx->places.start.p, ctx->places.recs.p, d_sums.p, ctl.p);
     MG_TRY(hipGetLastError());
   }
-  MG_TRY(hipEventRecord(ctx->pl_ev[1], st));
+  MG_TRY(ctx->places.ev.end(st));
   ull bad = ~0ull;
   std::vector<ull> h(3 * (size_t)n_datasets, 0);
-  MG_TRY(hipMemcpyAsync(&bad, ctl.p, sizeof(bad), hipMemcpyDeviceToHost, st));
   if (n_datasets) MG_TRY(hipMemcpyAsync(h.data(), d_sums.p, h.size() * sizeof(ull), hipMemcpyDeviceToHost, st));
-  MG_TRY(hipStreamSynchronize(st));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->pl_ev[0], ctx->pl_ev[1]));
+  MG_TRY(ctl_read(st, ctl.p, 1, &bad));
+  MG_TRY(ctx->places.ev.elapsed(device_ms));
   if (bad != ~0ull) {
     ctx->err = "mg_insert_sizes: mate entry " + std::to_string(bad) +
                ": its dataset is not below " + std::to_string(n_datasets) + " or its owner or mate ID lies outside 1.." +
@@ -520,82 +436,82 @@ int mg_edge_coverage(mg_ctx* ctx, const uint32_t* freq, uint64_t* out, float* de
   ctx->err.clear();
   if (device_ms) *device_ms = 0.f;
   MG_TRY(hipSetDevice(ctx->device));
-  if (!ctx->places_ready)
+  if (!ctx->places.ready)
     return set_err(ctx, "mg_edge_coverage: mg_build_placements must succeed for the current reads first");
-  const uint64_t n_edges = ctx->pl_edges.size(), E = ctx->n_places, N = ctx->n;
+  PlaceStage& pl = ctx->places;
+  const uint64_t n_edges = pl.edges.size(), E = pl.n, N = ctx->n;
   if (n_edges && !out) return set_err(ctx, "mg_edge_coverage: null argument");
   if (!freq && !(ctx->freq_ready && ctx->d_freq))
     return set_err(ctx, "mg_edge_coverage: no resident frequencies (the reads were not ingested on the device): "
                         "pass freq");
   for (uint64_t k = 0; k < n_edges; ++k)
-    if (ctx->pl_edges[k].offset >= kMaxOffset)
-      return set_err(ctx, "mg_edge_coverage: " + edge_name(ctx, k) + ": an offset of 2^40 or more is not supported");
+    if (pl.edges[k].offset >= kMaxOffset)
+      return set_err(ctx, "mg_edge_coverage: " + edge_name(pl.edges.data(), k) + ": an offset of 2^40 or more is not supported");
   hipStream_t st = ctx->stream;
-  const LenView v = view_of(ctx);
-  DevBuf<uint32_t> d_f;
-  DevBuf<EdgeInfo> d_info;
-  DevBuf<ull> d_fsum, ctl, d_out, delta;
-  DevBuf<uint64_t> d_cbase, cov;
-  DevBuf<uint8_t> tmp;
+  const ReadView v = view_of(ctx);
+  Scratch<uint32_t> d_f;
+  Scratch<EdgeInfo> d_info;
+  Scratch<ull> d_fsum, ctl, d_out, delta;
+  Scratch<uint64_t> d_cbase, cov;
+  Scratch<uint8_t> tmp;
   const uint32_t* fp = ctx->d_freq;
   if (freq) {
-    PL_ALLOC(d_f, N, "caller's read frequencies");
+    MG_SCRATCH(d_f, N, "caller's read frequencies");
     if (N) MG_TRY(hipMemcpyAsync(d_f.p, freq, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     fp = d_f.p;
   }
-  PL_ALLOC(d_info, n_edges, "coverage edge records");
-  PL_ALLOC(d_fsum, n_edges, "coverage frequency sums");
-  PL_ALLOC(d_out, 3 * n_edges, "coverage sums");
-  PL_ALLOC(d_cbase, n_edges + 1, "coverage counter bases");
-  PL_ALLOC(ctl, 3, "coverage control words");
+  MG_SCRATCH(d_info, n_edges, "coverage edge records");
+  MG_SCRATCH(d_fsum, n_edges, "coverage frequency sums");
+  MG_SCRATCH(d_out, 3 * n_edges, "coverage sums");
+  MG_SCRATCH(d_cbase, n_edges + 1, "coverage counter bases");
+  MG_SCRATCH(ctl, 3, "coverage control words");
   MG_TRY(hipMemsetAsync(d_fsum.p, 0, std::max<uint64_t>(n_edges, 1) * sizeof(ull), st));
   MG_TRY(hipMemsetAsync(d_out.p, 0, std::max<uint64_t>(3 * n_edges, 1) * sizeof(ull), st));
-  MG_TRY(hipMemsetAsync(ctl.p, 0xFF, 3 * sizeof(ull), st));
-  MG_TRY(hipEventRecord(ctx->pl_ev[0], st));
+  MG_TRY(ctl_fill(st, ctl.p, 3, ~0ull));
+  MG_TRY(pl.ev.start(st));
   if (n_edges) {
-    hipLaunchKernelGGL(k_cov_edges, dim3(blocks(n_edges)), dim3(kThreads), 0, st, v, ctx->d_pl_edges, n_edges, d_info.p,
+    hipLaunchKernelGGL(k_cov_edges, dim3(blocks_for(n_edges)), dim3(kThreads), 0, st, v, pl.d_edges.p, n_edges, d_info.p,
                        ctl.p);
     MG_TRY(hipGetLastError());
   }
   if (E) {
-    hipLaunchKernelGGL(k_cov_entries, dim3(blocks(E)), dim3(kThreads), 0, st, v, E, ctx->d_pl_eread, ctx->d_pl_eedge,
-                       ctx->d_pl_edist, d_info.p, fp, d_fsum.p, ctl.p);
+    hipLaunchKernelGGL(k_cov_entries, dim3(blocks_for(E)), dim3(kThreads), 0, st, v, E, pl.eread.p, pl.eedge.p,
+                       pl.edist.p, d_info.p, fp, d_fsum.p, ctl.p);
     MG_TRY(hipGetLastError());
   }
   ull bad[3] = {~0ull, ~0ull, ~0ull};
   std::vector<EdgeInfo> info(n_edges);
   std::vector<ull> fsum(n_edges, 0);
-  MG_TRY(hipMemcpyAsync(bad, ctl.p, sizeof(bad), hipMemcpyDeviceToHost, st));
   if (n_edges) {
     MG_TRY(hipMemcpyAsync(info.data(), d_info.p, n_edges * sizeof(EdgeInfo), hipMemcpyDeviceToHost, st));
     MG_TRY(hipMemcpyAsync(fsum.data(), d_fsum.p, n_edges * sizeof(ull), hipMemcpyDeviceToHost, st));
   }
-  MG_TRY(hipStreamSynchronize(st));
+  MG_TRY(ctl_read(st, ctl.p, 3, bad));
   if (bad[0] != ~0ull || bad[1] != ~0ull || bad[2] != ~0ull) {
     // the first invalid edge; within it: its IDs, then its first entry, then its source span
     const uint64_t ke =
         bad[0] == ~0ull ? ~0ull
-                        : (uint64_t)(std::upper_bound(ctx->pl_ebase.begin(), ctx->pl_ebase.end(), (uint64_t)bad[0]) -
-                                     ctx->pl_ebase.begin()) - 1;
+                        : (uint64_t)(std::upper_bound(pl.ebase.begin(), pl.ebase.end(), (uint64_t)bad[0]) -
+                                     pl.ebase.begin()) - 1;
     const uint64_t k = std::min<uint64_t>(ke, std::min<uint64_t>(bad[1], bad[2]));
     std::string why;
     if (k == bad[1]) why = ": its source or destination read ID lies outside 1.." + std::to_string(N);
     else if (k == ke)
-      why = ", list entry " + std::to_string(bad[0] - ctx->pl_ebase[k]) +
+      why = ", list entry " + std::to_string(bad[0] - pl.ebase[k]) +
             ": the read ends beyond the edge's counters (vector::at would throw)";
     else why = ": the source read is longer than the edge's counters (vector::at would throw)";
-    ctx->err = "mg_edge_coverage: " + edge_name(ctx, k) + why + " (-2)";
+    ctx->err = "mg_edge_coverage: " + edge_name(pl.edges.data(), k) + why + " (-2)";
     return -2;
   }
   for (uint64_t k = 0; k < n_edges; ++k)
     if (fsum[k] >> 32)
-      return set_err(ctx, "mg_edge_coverage: " + edge_name(ctx, k) +
+      return set_err(ctx, "mg_edge_coverage: " + edge_name(pl.edges.data(), k) +
                               ": its list frequencies sum to 2^32 or more (the per-base counters are 32 bits wide)");
   // counters of edge k at cbase[k]; an edge without list reads owns none
   std::vector<uint64_t> cbase(n_edges + 1, 0);
-  for (uint64_t k = 0; k < n_edges; ++k) cbase[k + 1] = cbase[k] + (ctx->pl_edges[k].n ? info[k].L + 1 : 0);
+  for (uint64_t k = 0; k < n_edges; ++k) cbase[k + 1] = cbase[k] + (pl.edges[k].n ? info[k].L + 1 : 0);
   MG_TRY(hipMemcpyAsync(d_cbase.p, cbase.data(), (n_edges + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-  const uint64_t budget = ctx->cov_budget ? ctx->cov_budget : kCovBudget;
+  const uint64_t budget = pl.cov_budget ? pl.cov_budget : kCovBudget;
   uint64_t chunk_cap = 0;
   for (uint64_t k0 = 0; k0 < n_edges;) {  // sizes first: one allocation serves every chunk
     uint64_t k1 = k0 + 1;
@@ -604,34 +520,34 @@ int mg_edge_coverage(mg_ctx* ctx, const uint32_t* freq, uint64_t* out, float* de
     k0 = k1;
   }
   size_t tmp_bytes = 0;
-  PL_ALLOC(delta, chunk_cap + 1, "coverage delta words");
-  PL_ALLOC(cov, chunk_cap + 1, "coverage counters");
+  MG_SCRATCH(delta, chunk_cap + 1, "coverage delta words");
+  MG_SCRATCH(cov, chunk_cap + 1, "coverage counters");
   MG_TRY(hipcub::DeviceScan::InclusiveSum(nullptr, tmp_bytes, delta.p, cov.p, (int64_t)std::max<uint64_t>(chunk_cap, 1),
                                           st));
-  PL_ALLOC(tmp, tmp_bytes, "coverage scan storage");
+  MG_SCRATCH(tmp, tmp_bytes, "coverage scan storage");
   for (uint64_t k0 = 0; k0 < n_edges;) {
     uint64_t k1 = k0 + 1;
     while (k1 < n_edges && cbase[k1 + 1] - cbase[k0] <= budget) ++k1;
-    const uint64_t B = cbase[k1] - cbase[k0], e0 = ctx->pl_ebase[k0], e1 = ctx->pl_ebase[k1];
+    const uint64_t B = cbase[k1] - cbase[k0], e0 = pl.ebase[k0], e1 = pl.ebase[k1];
     if (B) {
       MG_TRY(hipMemsetAsync(delta.p, 0, (B + 1) * sizeof(ull), st));
       if (e1 > e0) {
-        hipLaunchKernelGGL(k_cov_delta, dim3(blocks(e1 - e0)), dim3(kThreads), 0, st, v, e0, e1, ctx->d_pl_eread,
-                           ctx->d_pl_eedge, ctx->d_pl_edist, d_cbase.p, cbase[k0], fp, ctx->d_pl_fwd, delta.p);
+        hipLaunchKernelGGL(k_cov_delta, dim3(blocks_for(e1 - e0)), dim3(kThreads), 0, st, v, e0, e1, pl.eread.p,
+                           pl.eedge.p, pl.edist.p, d_cbase.p, cbase[k0], fp, pl.fwd.p, delta.p);
         MG_TRY(hipGetLastError());
       }
       size_t tb = tmp_bytes;
       MG_TRY(hipcub::DeviceScan::InclusiveSum(tmp.p, tb, delta.p, cov.p, (int64_t)B, st));
-      hipLaunchKernelGGL(k_cov_reduce, dim3(blocks(B)), dim3(kThreads), 0, st, cov.p, B, k0, k1, d_cbase.p, cbase[k0],
+      hipLaunchKernelGGL(k_cov_reduce, dim3(blocks_for(B)), dim3(kThreads), 0, st, cov.p, B, k0, k1, d_cbase.p, cbase[k0],
                          d_info.p, d_out.p);
       MG_TRY(hipGetLastError());
     }
     k0 = k1;
   }
-  MG_TRY(hipEventRecord(ctx->pl_ev[1], st));
+  MG_TRY(pl.ev.end(st));
   if (n_edges) MG_TRY(hipMemcpyAsync(out, d_out.p, 3 * n_edges * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
   MG_TRY(hipStreamSynchronize(st));
-  if (device_ms) MG_TRY(hipEventElapsedTime(device_ms, ctx->pl_ev[0], ctx->pl_ev[1]));
+  MG_TRY(pl.ev.elapsed(device_ms));
   return 0;
 }
 
