@@ -243,3 +243,7 @@ def test_read_count_edges(engine, N):
     assert s.n == N
     got = device_components(engine, s.ds, COUNT_L, k=COUNT_K)
     assert_components(got, s.want)
+    # the lists the components were labelled from
+    start, disc, _ = numpy_lists(s.rows, s.lens, COUNT_L)
+    got_start, got_disc = engine.discoveries()
+    assert np.array_equal(got_start, start) and np.array_equal(got_disc, disc)
