@@ -558,6 +558,10 @@ int mg_get_counters(const mg_ctx* ctx, mg_counters* c);
  *                   hits (default); 0 = the probe verifies them itself;
  *  "contain_jcut", "contain_prune", "contain_skip"
  *                   containment pruning, all exact, default 1;
+ *  "run_masks"      the window scan records a read's minimizer positions in a
+ *                   per-lane bit set and emits its runs after the read (reads up
+ *                   to 256 bp, l - k <= 32; default 1); 0 = every closed run is
+ *                   staged in LDS.  Same run records, in another order;
  *  "probe_share"    a discovery block's 4 wavefronts share its run regions (default 1);
  *  "probe_compact"  sparse run batches are compacted in the probe (default 1);
  *  "live_index"     mixed lengths: after mg_mark_contained the discovery probe

@@ -367,6 +367,7 @@ struct mg_ctx {
   // its runs then serve the containment and the discovery probes
   int scan_state = 0;        // 0 none, 1 launched (not settled), 2 settled
   bool runs_live = false;    // the run regions hold only runs of uncontained sources (k_live_runs)
+  bool run_masks = true;       // option "run_masks": k_scan records runs as per-lane bit sets (0: staged in LDS)
   bool probe_share = true;     // option "probe_share": a discovery-probe block's 4 wavefronts share its regions
   bool probe_compact = true;   // option "probe_compact": sparse run batches compacted in the probe (C5 probe 30.4 -> 26.8 ms)
   // prefix containments (k_prefix_contain): each read's o = 0 key (bucket,

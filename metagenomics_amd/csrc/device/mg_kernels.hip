@@ -42,6 +42,7 @@
 
 #include "mg_ctx.hpp"
 #include "mg_overlap.h"
+#include "mg_runs.hpp"
 
 // two window steps per loop trip in the scan (A/B builds: -DMG_SCAN_UNROLL=2).
 // Measured: C3 scan level (2.19-2.21 vs 2.21-2.23 ms), C5 -0.14 ms of 15.8
@@ -966,8 +967,20 @@ __device__ __forceinline__ uint64_t ext_reg(const uint64_t* rw, int pos) {
 #ifndef MG_SCAN_WAVES_G
 #define MG_SCAN_WAVES_G 6  // waves/SIMD of the length-ranked (G > 1) scan (A/B builds override)
 #endif
-template <int MAXW, bool INDEX, bool KEYREC = false, int G = 1, bool RECV = false>
+// MASKS (option run_masks, w <= kMaskW, MAXW <= 8): the base loop records a
+// read's runs as one per-lane bit set, the minimizer positions (mg_runs.hpp:
+// an add, a shift and two ORs per step in place of a ballot-compacted LDS
+// store; while every lane of the wavefront is inside its read, nothing else),
+// and after the read every lane emits its own runs, one per trip: next bit of
+// the set, the m-mer from its own words, its order key -- which, against the
+// run before, says where that run ended -- hash, one full-wavefront store.  No
+// staging buffer: the scan's LDS is its suffix minima alone.  A region's
+// records are then ordered by run ordinal across the 64 reads instead of by
+// closing step.
+constexpr int kMaskW = 32;  // successive minimizers lie at most w apart: one chunk shift per run
+template <int MAXW, bool INDEX, bool KEYREC = false, int G = 1, bool RECV = false, bool MASKS = false>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? MG_SCAN_WAVES_G : 6))) void k_scan(ScanParams p) {
+  static_assert(!MASKS || MAXW <= 8, "the mask path keeps a read's words and both bit sets in registers");
   extern __shared__ __attribute__((aligned(16))) uint64_t smem[];
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   const int h = p.h, m = p.m, w = p.w;
@@ -1092,7 +1105,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
     const uint32_t wslot = key & 255u;
     const uint64_t a = A0 + wslot;
     const int n = (int)(0x7FFu - (key >> 8));
-    const uint64_t own = G > 1 ? ((uint64_t)lane << 8) | wslot : a;  // a staged run's read (see put)
+    const uint64_t own = (G > 1 && !MASKS) ? ((uint64_t)lane << 8) | wslot : a;  // a staged run's read (see put)
     const uint64_t* g = p.words + a * slot_words(MAXW);
     const int J = n - h - 1;                 // windows j = 1 .. J (:534)
     const int tend = J >= 1 ? J + w - 1 : 0;  // last m-mer position a window uses
@@ -1102,6 +1115,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) tmax = max(tmax, __shfl_xor(tmax, d));
     tmax = __builtin_amdgcn_readfirstlane(tmax);  // wavefront-uniform loop bound
+    // MASKS: up to t = tall every lane that has windows is inside its read
+    int tall = 0;
+    if constexpr (MASKS) {
+      tall = tend ? tend : 0x7FFFFFFF;
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) tall = min(tall, __shfl_xor(tall, d));
+      tall = __builtin_amdgcn_readfirstlane(tall);
+    }
     // the read's words in registers (no global load inside the base loop); the
     // word holding base t + m is picked by a wavefront-uniform index
     constexpr int kRw = MAXW + 1 <= slot_words(MAXW) ? MAXW + 1 : slot_words(MAXW);
@@ -1121,6 +1142,61 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
 #pragma unroll
       for (int k = 1; k <= MAXW; ++k) v = idx == k ? rw[k] : v;
       return v;
+    };
+    // one record per flagged lane (v = its hash, meta, grp = its group in the
+    // window): full-wavefront, ballot-compacted stores into the group's region
+    auto store_run = [&](bool flag, uint64_t v, uint64_t meta, uint32_t grp_in) {
+      uint64_t at_rec = 0;  // the record's index in its region
+      uint32_t grp_rec = 0;
+      if constexpr (G == 1) {
+        const uint64_t bal = __ballot(flag);
+        const uint64_t at = cur[0] + lane_prefix(bal);
+        at_rec = at;
+        if constexpr (RECV) {  // the meta and its owner rank (the hash stays here: the owner re-hashes)
+          if (flag && at < p.run_cap) {
+            reinterpret_cast<uint64_t*>(p.runs)[gw * p.run_cap + at] = meta;
+            p.run_dst[gw * p.run_cap + at] = (uint8_t)(((v & nbmask) * p.dst_ranks) >> p.nb_log2);
+          }
+        } else {
+#if defined(MG_DIAG_STORE_NEVER)
+        if (flag && at < p.run_cap && v == 0x0123456789ABCDEFull) region[at] = make_ulonglong2(v, meta);
+#elif !defined(MG_DIAG_NO_RUNSTORE)
+        if (flag && at < p.run_cap) region[at] = make_ulonglong2(v, meta);
+#endif
+        }
+        cur[0] += (uint64_t)__popcll(bal);
+      } else {
+#ifdef MG_DIAG_ONE_REGION  // (diagnostics build: every run of a window into its first region)
+        const uint32_t grp = 0;
+#else
+        const uint32_t grp = grp_in;  // the run's group in the window
+#endif
+        uint64_t at = 0;
+#pragma unroll
+        for (int j = 0; j < G; ++j) {
+          const uint64_t bal = __ballot(flag && grp == (uint32_t)j);
+          if (grp == (uint32_t)j) at = cur[j] + lane_prefix(bal);
+          cur[j] += (uint64_t)__popcll(bal);
+        }
+        at_rec = at;
+        grp_rec = grp;
+#if defined(MG_DIAG_STORE_NEVER)  // (diagnostics build: runs hashed and placed, but (practically) never stored)
+        if (flag && at < p.run_cap && v == 0x0123456789ABCDEFull) region[grp * p.run_cap + at] = make_ulonglong2(v, meta);
+#elif !defined(MG_DIAG_NO_RUNSTORE)  // (diagnostics build: the window scan stores no runs)
+        if (flag && at < p.run_cap) region[grp * p.run_cap + at] = make_ulonglong2(v, meta);
+#endif
+      }
+      if constexpr (KEYREC || RECV) {
+        if (p.dst_cnt) {
+          const bool st = flag && at_rec < p.run_cap;  // (k_part routes the stored records of a region)
+          const uint32_t d = st ? (uint32_t)(((v & nbmask) * p.dst_ranks) >> p.nb_log2) : 0u;
+          for (uint32_t jj = 0; jj < (uint32_t)G; ++jj)
+            for (uint32_t dd = 0; dd < p.dst_ranks; ++dd) {
+              const uint32_t cc = (uint32_t)__popcll(__ballot(st && grp_rec == jj && d == dd));
+              dcnt += (uint32_t)lane == jj * p.dst_ranks + dd ? cc : 0u;
+            }
+        }
+      }
     };
     // hash the first k (<= 64) staged runs with every lane busy, drop runs whose
     // bucket another rank owns, write full-wavefront 16-B records into the
@@ -1159,57 +1235,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
         v = mix64(funnel(g2[pos >> 5], g2[(pos >> 5) + 1], (pos & 31) << 1) >> msh);
         if (!INDEX || p.nranks > 1) flag = owned(v & nbmask, p.nb_log2, p.rank, p.nranks);
       }
-      uint64_t at_rec = 0;  // the record's index in its region
-      uint32_t grp_rec = 0;
-      if constexpr (G == 1) {
-        const uint64_t bal = __ballot(flag);
-        const uint64_t at = cur[0] + lane_prefix(bal);
-        at_rec = at;
-        if constexpr (RECV) {  // the meta and its owner rank (the hash stays here: the owner re-hashes)
-          if (flag && at < p.run_cap) {
-            reinterpret_cast<uint64_t*>(p.runs)[gw * p.run_cap + at] = meta;
-            p.run_dst[gw * p.run_cap + at] = (uint8_t)(((v & nbmask) * p.dst_ranks) >> p.nb_log2);
-          }
-        } else {
-#if defined(MG_DIAG_STORE_NEVER)
-        if (flag && at < p.run_cap && v == 0x0123456789ABCDEFull) region[at] = make_ulonglong2(v, meta);
-#elif !defined(MG_DIAG_NO_RUNSTORE)
-        if (flag && at < p.run_cap) region[at] = make_ulonglong2(v, meta);
-#endif
-        }
-        cur[0] += (uint64_t)__popcll(bal);
-      } else {
-#ifdef MG_DIAG_ONE_REGION  // (diagnostics build: every run of a window into its first region)
-        const uint32_t grp = 0;
-#else
-        const uint32_t grp = ws >> 6;  // the run's group in the window
-#endif
-        uint64_t at = 0;
-#pragma unroll
-        for (int j = 0; j < G; ++j) {
-          const uint64_t bal = __ballot(flag && grp == (uint32_t)j);
-          if (grp == (uint32_t)j) at = cur[j] + lane_prefix(bal);
-          cur[j] += (uint64_t)__popcll(bal);
-        }
-        at_rec = at;
-        grp_rec = grp;
-#if defined(MG_DIAG_STORE_NEVER)  // (diagnostics build: runs hashed and placed, but (practically) never stored)
-        if (flag && at < p.run_cap && v == 0x0123456789ABCDEFull) region[grp * p.run_cap + at] = make_ulonglong2(v, meta);
-#elif !defined(MG_DIAG_NO_RUNSTORE)  // (diagnostics build: the window scan stores no runs)
-        if (flag && at < p.run_cap) region[grp * p.run_cap + at] = make_ulonglong2(v, meta);
-#endif
-      }
-      if constexpr (KEYREC || RECV) {
-        if (p.dst_cnt) {
-          const bool st = flag && at_rec < p.run_cap;  // (k_part routes the stored records of a region)
-          const uint32_t d = st ? (uint32_t)(((v & nbmask) * p.dst_ranks) >> p.nb_log2) : 0u;
-          for (uint32_t jj = 0; jj < (uint32_t)G; ++jj)
-            for (uint32_t dd = 0; dd < p.dst_ranks; ++dd) {
-              const uint32_t cc = (uint32_t)__popcll(__ballot(st && grp_rec == jj && d == dd));
-              dcnt += (uint32_t)lane == jj * p.dst_ranks + dd ? cc : 0u;
-            }
-        }
-      }
+      store_run(flag, v, meta, ws >> 6);
       const uint32_t rest = nbuf - k;  // < 128 left: move them to the front
       const uint64_t m0 = (uint32_t)lane < rest ? s_buf[k + lane] : 0;
       const uint64_t m1 = (uint32_t)lane + kWave < rest ? s_buf[k + kWave + lane] : 0;
@@ -1233,6 +1259,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
     if (INDEX && tend) kb0 = order_key(rw[0] >> msh);  // t = 0 (window j = 0 is no scan window)
     uint32_t pmin = 0xFFFFFFFFu;
     int last_pos = 0, jlo = 1;
+    uint32_t last_mn = 0;  // MASKS: the last window minimum (key | position) the lane saw inside its read
     int u = 0;  // offset of t in its block of w positions
     // previous block's suffix minimum at u + 1, read one step ahead so the
     // LDS latency hides behind the step's ALU work
@@ -1269,11 +1296,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
       sv_pf = s_keys[(u + 1) * kWave];  // (u + 1 = w: the sentinel)
     };
     // t = 1 .. w: the first block; t = w is window j = 1 (no run closes there)
-    auto step_first = [&](int t, uint64_t cw, int sh) {
+    // (MASKS: plo / phi = the P chunks (t + m) / 32 - 1 and (t + m) / 32, cadd =
+    // m minus the first bit of plo: position p is bit p + cadd of the pair)
+    auto step_first = [&](int t, uint64_t cw, int sh, uint32_t& plo, uint32_t& phi, int cadd) {
       const uint32_t key = order_key(mm) | (uint32_t)t;
       pmin = min(pmin, key);
       if (INDEX && t == w - 1) kb0 = min(kb0, pmin);  // o = 0: t in [0, w)
-      if (t == w) last_pos = (int)(min(sv_pf, pmin) & 1023u);
+      if (t == w) {
+        last_mn = min(sv_pf, pmin);
+        last_pos = (int)(last_mn & 1023u);
+        if constexpr (MASKS) mg_runs::mark(plo, phi, last_mn + (uint32_t)cadd);  // (a read without windows: clipped away)
+      }
       roll_and_advance(key, cw, sh);
     };
     // t > w: window j = t - w + 1 >= 2 (a run closes where its minimizer moves)
@@ -1292,6 +1325,30 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
       put(emit, e_meta);
       if (nbuf >= (uint32_t)kWave) flush(kWave);  // (< 64 staged before the put: one flush at most)
     };
+    // the same step recording the minimizer position in P (idempotent: no
+    // predicate; last_mn = the window minimum, position in its low bits, which
+    // are all mg_runs::mark reads).  step_all: every lane that has windows is
+    // inside its read (t <= tall), so nothing is held and o = 1's window is
+    // not reached.  step_m: a lane past its read holds its last minimum; what
+    // that sets in P lies above its position and is clipped after the loop.
+    auto step_all = [&](int t, uint64_t cw, int sh, uint32_t& plo, uint32_t& phi, int cadd) {
+      const uint32_t key = order_key(mm) | (uint32_t)t;
+      pmin = min(pmin, key);
+      last_mn = min(sv_pf, pmin);
+      mg_runs::mark(plo, phi, last_mn + (uint32_t)cadd);
+      roll_and_advance(key, cw, sh);
+    };
+    auto step_m = [&](int t, uint64_t cw, int sh, uint32_t& plo, uint32_t& phi, int cadd) {
+      const uint32_t key = order_key(mm) | (uint32_t)t;
+      pmin = min(pmin, key);
+      const uint32_t mn = min(sv_pf, pmin);
+      if (INDEX) kb1 = t == tlast ? mn - (uint32_t)(n - h) : kb1;  // o = 1: window j = n - h, i = t - (n - h)
+      last_mn = t <= tend ? mn : last_mn;
+      mg_runs::mark(plo, phi, last_mn + (uint32_t)cadd);
+      roll_and_advance(key, cw, sh);
+    };
+    constexpr int NC = MASKS ? MAXW : 1;  // 32-bit chunks of the set: bits [0, 32 MAXW) hold p + m <= n - 1
+    uint32_t Pc[NC] = {};
     if constexpr (MAXW <= 8) {
       // one loop per read word and phase (t + m <= n - 1 < 32 MAXW): the word is
       // a compile-time register, so rw[] never goes to scratch and no vmcnt wait
@@ -1300,9 +1357,20 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
       for (int k = 0; k < MAXW + (INDEX ? 1 : 0); ++k) {  // (INDEX's step t = n - m rolls in base n)
         const int t0 = max(1, 32 * k - m), t1 = min(tmax, 32 * k + 31 - m);
         const int tf = min(t1, w);
-        for (int t = t0, sh = 62 - 2 * ((t0 + m) & 31); t <= tf; ++t, sh -= 2) step_first(t, rw[k], sh);
+        // MASKS: this word's steps set bits in the chunks k - 1 and k (w <= 33:
+        // p + m in [t + m - w + 1, t + m]); past the last chunk (INDEX's extra
+        // word) every lane is past its read
+        uint32_t spare_lo = 0, spare_hi = 0;
+        uint32_t& plo = (MASKS && k >= 1 && k - 1 < NC) ? Pc[k >= 1 && k - 1 < NC ? k - 1 : 0] : spare_lo;
+        uint32_t& phi = (MASKS && k < NC) ? Pc[k < NC ? k : 0] : spare_hi;
+        const int cadd = m + 32 - 32 * k;
+        for (int t = t0, sh = 62 - 2 * ((t0 + m) & 31); t <= tf; ++t, sh -= 2) step_first(t, rw[k], sh, plo, phi, cadd);
         int t = max(t0, w + 1), sh = 62 - 2 * ((t + m) & 31);
-        if (t <= t1) {
+        if constexpr (MASKS) {
+          const int tq = min(t1, tall);
+          for (; t <= tq; ++t, sh -= 2) step_all(t, rw[k], sh, plo, phi, cadd);
+          for (; t <= t1; ++t, sh -= 2) step_m(t, rw[k], sh, plo, phi, cadd);
+        } else if (t <= t1) {
 #if MG_SCAN_UNROLL == 2
           // two steps per trip: half the loop's scalar counting and branching
           for (; t + 1 <= t1; t += 2, sh -= 4) {
@@ -1323,13 +1391,16 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
       uint64_t cw = word_at(cwi);
       for (int t = 1; t <= tmax; ++t) {
         const int sh = 62 - 2 * ((t + m) & 31);
-        if (t <= w) step_first(t, cw, sh); else step(t, cw, sh);
+        uint32_t spare = 0;  // (no bit sets at these widths)
+        if (t <= w) step_first(t, cw, sh, spare, spare, 0); else step(t, cw, sh);
         const int xu = __builtin_amdgcn_readfirstlane(t + m);
         if ((xu & 31) == 31) cw = word_at((xu + 1) >> 5);  // next word (don't-care past a read's end)
       }
     }
-    put(tend > 0, run_meta(own, last_pos, jlo, J));  // each read's last run
-    while (nbuf) flush(nbuf < (uint32_t)kWave ? nbuf : (uint32_t)kWave);  // the group's runs leave with its registers
+    if constexpr (!MASKS) {
+      put(tend > 0, run_meta(own, last_pos, jlo, J));  // each read's last run
+      while (nbuf) flush(nbuf < (uint32_t)kWave ? nbuf : (uint32_t)kWave);  // the group's runs leave with its registers
+    }
     if (INDEX && tend) {
       // o = 3 (R[n-h, n) = rc F[0, h): m-mer i = rc of F's at t = w-1-i) and
       // o = 2 (R[0, h) = rc F[n-h, n): m-mer i = rc of F's at t = n-m-i), both
@@ -1402,6 +1473,55 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(G > 1 ? 
           p.key_bk[key_seg(o) * p.key_n + a - p.key_lo] = 0;
           p.key_ent[key_seg(o) * p.key_n + a - p.key_lo] = kEmpty;
         }
+      }
+    }
+    if constexpr (MASKS) {
+      // Emission, after the keys (it uses up the read's words): one run per
+      // lane and trip, as many trips as the wavefront's longest run list.  The
+      // words travel with P's chunks -- R[1] is the word of chunk 0, R[0] the
+      // one before it -- so the m-mer ending at bit x of chunk 0 is the low 2m
+      // bits of funnel(R[0], R[1], 2 x): no per-lane word index.  A run's last
+      // window comes from the run after it (mg_runs::run_end).
+      mg_runs::clip<NC>(Pc, (int)(last_mn & 1023u) + m, tend > 0);
+      const uint32_t cnt = mg_runs::count<NC>(Pc);
+      int trips = (int)cnt;
+#pragma unroll
+      for (int d = 32; d >= 1; d >>= 1) trips = max(trips, __shfl_xor(trips, d));
+      trips = __builtin_amdgcn_readfirstlane(trips);
+      uint64_t R[MAXW + 1];
+      R[0] = 0;
+#pragma unroll
+      for (int k = 0; k < MAXW; ++k) R[k + 1] = rw[k];
+      auto carry = [&](bool sft) {
+#pragma unroll
+        for (int k = 0; k < MAXW; ++k) R[k] = sft ? R[k + 1] : R[k];
+      };
+      int xb = 0, jl = 1;
+      // leading empty chunks: the first position is at most w (bit <= w + m <= 64)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) mg_runs::shift<NC>(Pc, xb, carry);
+      // the next run of the lane: its position, m-mer and key (order key | position)
+      auto take = [&](int& rp, uint64_t& rm, uint32_t& rk) {
+        const int x = mg_runs::pop<NC, 0>(Pc, xb, carry);
+        rp = x - m;
+        rm = funnel(R[0], R[1], (x & 31) << 1) & mmask;
+        rk = order_key(rm) | (uint32_t)rp;
+      };
+      int pc, pn;
+      uint64_t mc, mnx;
+      uint32_t kc, kn;
+      take(pc, mc, kc);
+      for (int i = 0; i < trips; ++i) {  // run i leaves once run i + 1 says where it ended
+        take(pn, mnx, kn);
+        bool flag = (uint32_t)i < cnt;
+        const int jh = mg_runs::run_end(pc, kc, pn, kn, (uint32_t)i + 1 >= cnt, J, w);
+        const uint64_t v = mix64(mc);
+        if (!INDEX || p.nranks > 1) flag = flag && owned(v & nbmask, p.nb_log2, p.rank, p.nranks);
+        store_run(flag, v, run_meta(a, pc, jl, jh), wslot >> 6);
+        jl = jh + 1;
+        pc = pn;
+        mc = mnx;
+        kc = kn;
       }
     }
    }
@@ -3360,13 +3480,19 @@ uint32_t resident_blocks(mg_ctx* ctx, K kernel, size_t lds, uint64_t want, int b
 // run metas; blocks carry 4 wavefronts, or 2 / 1 when that does not fit
 // (long windows: w = l - k grows with min_overlap).  0 = w too large.
 constexpr size_t kLdsPerCu = 160 * 1024;
-inline size_t scan_lds_per_wave(uint32_t w) {
-  return (((size_t)(w + kScanKeyPad) * kWave + 1) / 2 + kScanBuf) * sizeof(uint64_t);
+// (masks: the mask path stages nothing, its LDS is the suffix minima alone)
+inline size_t scan_lds_per_wave(uint32_t w, bool masks = false) {
+  return (((size_t)(w + kScanKeyPad) * kWave + 1) / 2 + (masks ? 0 : kScanBuf)) * sizeof(uint64_t);
 }
-inline uint32_t scan_wpb(uint32_t w) {
+inline uint32_t scan_wpb(uint32_t w, bool masks = false) {
   for (uint32_t wpb = kWavesPerBlock; wpb >= 1; wpb >>= 1)
-    if (wpb * scan_lds_per_wave(w) <= kLdsPerCu) return wpb;
+    if (wpb * scan_lds_per_wave(w, masks) <= kLdsPerCu) return wpb;
   return 0;
+}
+// k_scan<..., MASKS> runs where the bit sets fit registers and one chunk shift
+// per run suffices (option run_masks; else the staged path)
+inline bool scan_masks(const mg_ctx* ctx) {
+  return ctx->run_masks && ctx->maxw <= 8 && ctx->w <= (uint32_t)kMaskW;
 }
 // Which window scan runs.  The index-building scan of the fused path is
 // k_scan<INDEX> (LDS sliding minimum, CAS inserts hidden behind its ALU work);
@@ -3388,11 +3514,21 @@ inline int scan_windows(const mg_ctx* ctx, bool index) {
   return (index && ctx->minlen != ctx->maxlen && !scan_is_reg(ctx, index)) ? kWinGroups : 1;
 }
 inline uint32_t scan_block_waves(const mg_ctx* ctx, bool index) {
-  return scan_is_reg(ctx, index) ? kWavesPerBlock : scan_wpb(ctx->w);
+  return scan_is_reg(ctx, index) ? kWavesPerBlock : scan_wpb(ctx->w, scan_masks(ctx));
 }
 inline size_t scan_lds(const mg_ctx* ctx, bool index) {
   return scan_is_reg(ctx, index) ? (size_t)kWavesPerBlock * kStageRing * sizeof(uint64_t)
-                                 : (size_t)scan_wpb(ctx->w) * scan_lds_per_wave(ctx->w);
+                                 : (size_t)scan_wpb(ctx->w, scan_masks(ctx)) * scan_lds_per_wave(ctx->w, scan_masks(ctx));
+}
+template <int W, bool M>
+uint32_t scan_resident_k(mg_ctx* ctx, bool index, uint64_t want, size_t lds, int block) {
+  if (index && ctx->xchg)
+    return scan_windows(ctx, index) > 1 ? resident_blocks(ctx, k_scan<W, true, true, kWinGroups, false, M>, lds, want, block)
+                                        : resident_blocks(ctx, k_scan<W, true, true, 1, false, M>, lds, want, block);
+  if (ctx->rk_on) return resident_blocks(ctx, k_scan<W, false, false, 1, true, M>, lds, want, block);
+  return index ? (scan_windows(ctx, index) > 1 ? resident_blocks(ctx, k_scan<W, true, false, kWinGroups, false, M>, lds, want, block)
+                                                : resident_blocks(ctx, k_scan<W, true, false, 1, false, M>, lds, want, block))
+               : resident_blocks(ctx, k_scan<W, false, false, 1, false, M>, lds, want, block);
 }
 template <int W>
 uint32_t scan_resident(mg_ctx* ctx, bool index, uint64_t want) {
@@ -3401,13 +3537,10 @@ uint32_t scan_resident(mg_ctx* ctx, bool index, uint64_t want) {
   if (scan_is_reg(ctx, index))
     return index ? resident_blocks(ctx, k_scan_reg<W, true>, lds, want, block)
                  : resident_blocks(ctx, k_scan_reg<W, false>, lds, want, block);
-  if (index && ctx->xchg)
-    return scan_windows(ctx, index) > 1 ? resident_blocks(ctx, k_scan<W, true, true, kWinGroups>, lds, want, block)
-                                        : resident_blocks(ctx, k_scan<W, true, true>, lds, want, block);
-  if (ctx->rk_on) return resident_blocks(ctx, k_scan<W, false, false, 1, true>, lds, want, block);
-  return index ? (scan_windows(ctx, index) > 1 ? resident_blocks(ctx, k_scan<W, true, false, kWinGroups>, lds, want, block)
-                                                : resident_blocks(ctx, k_scan<W, true>, lds, want, block))
-               : resident_blocks(ctx, k_scan<W, false>, lds, want, block);
+  if constexpr (W <= 8) {
+    if (scan_masks(ctx)) return scan_resident_k<W, true>(ctx, index, want, lds, block);
+  }
+  return scan_resident_k<W, false>(ctx, index, want, lds, block);
 }
 
 // Geometry of one discovery pass over source reads [a_lo, a_hi): probe grid =
@@ -3449,6 +3582,31 @@ uint32_t fp_sort_bits(uint32_t hb) {
 // (fused: CAS into the cells; exchange: key records).
 template <int W>
 struct LaunchScan {
+  // the k_scan instantiation of a pass (M: the mask path)
+  template <bool M>
+  static void launch_k(mg_ctx* ctx, bool index, bool recv, bool windows, uint32_t sgrid, uint32_t wpb, size_t lds,
+                       hipStream_t stream, const ScanParams& sp) {
+    const dim3 grid(sgrid), block(wpb * kWave);
+    if (index && ctx->xchg && windows) {
+      allow_lds(k_scan<W, true, true, kWinGroups, false, M>, lds);
+      hipLaunchKernelGGL((k_scan<W, true, true, kWinGroups, false, M>), grid, block, lds, stream, sp);
+    } else if (index && ctx->xchg) {
+      allow_lds(k_scan<W, true, true, 1, false, M>, lds);
+      hipLaunchKernelGGL((k_scan<W, true, true, 1, false, M>), grid, block, lds, stream, sp);
+    } else if (recv) {
+      allow_lds(k_scan<W, false, false, 1, true, M>, lds);
+      hipLaunchKernelGGL((k_scan<W, false, false, 1, true, M>), grid, block, lds, stream, sp);
+    } else if (index && windows) {
+      allow_lds(k_scan<W, true, false, kWinGroups, false, M>, lds);
+      hipLaunchKernelGGL((k_scan<W, true, false, kWinGroups, false, M>), grid, block, lds, stream, sp);
+    } else if (index) {
+      allow_lds(k_scan<W, true, false, 1, false, M>, lds);
+      hipLaunchKernelGGL((k_scan<W, true, false, 1, false, M>), grid, block, lds, stream, sp);
+    } else {
+      allow_lds(k_scan<W, false, false, 1, false, M>, lds);
+      hipLaunchKernelGGL((k_scan<W, false, false, 1, false, M>), grid, block, lds, stream, sp);
+    }
+  }
   static int run(mg_ctx* ctx, bool contain, uint64_t a_lo, uint64_t a_hi, uint32_t sgrid, bool filter,
                  hipStream_t stream = nullptr, bool no_super = false, bool index = false) {
     if (!stream) stream = ctx->stream;
@@ -3546,33 +3704,24 @@ struct LaunchScan {
         allow_lds(k_scan_reg<W, false>, lds);
         hipLaunchKernelGGL((k_scan_reg<W, false>), dim3(sgrid), dim3(wpb * kWave), lds, stream, sp);
       }
-    } else if (index && ctx->xchg && G > 1) {
-      allow_lds(k_scan<W, true, true, kWinGroups>, lds);
-      hipLaunchKernelGGL((k_scan<W, true, true, kWinGroups>), dim3(sgrid), dim3(wpb * kWave), lds, stream, sp);
-    } else if (index && ctx->xchg) {
-      allow_lds(k_scan<W, true, true>, lds);
-      hipLaunchKernelGGL((k_scan<W, true, true>), dim3(sgrid), dim3(wpb * kWave), lds, stream, sp);
-    } else if (recv) {  // exchange mode, keys first: the runs + the received keys' CAS inserts
-      MG_ENSURE(d_rdst, rdst_cap, run_cap * nreg);
-      sp.run_dst = ctx->d_rdst;
-      ctx->runs_meta8 = true;
-      sp.recv_keys = ctx->rk_keys;
-      sp.recv_cnt = ctx->rk_cnt;
-      sp.recv_slot = ctx->rk_slot;
-      sp.recv_total = ctx->rk_total;
-      sp.recv_P = ctx->nranks;
-      sp.cell_lo = ctx->cell_lo;
-      allow_lds(k_scan<W, false, false, 1, true>, lds);
-      hipLaunchKernelGGL((k_scan<W, false, false, 1, true>), dim3(sgrid), dim3(wpb * kWave), lds, stream, sp);
-    } else if (index && G > 1) {
-      allow_lds(k_scan<W, true, false, kWinGroups>, lds);
-      hipLaunchKernelGGL((k_scan<W, true, false, kWinGroups>), dim3(sgrid), dim3(wpb * kWave), lds, stream, sp);
-    } else if (index) {
-      allow_lds(k_scan<W, true>, lds);
-      hipLaunchKernelGGL((k_scan<W, true>), dim3(sgrid), dim3(wpb * kWave), lds, stream, sp);
     } else {
-      allow_lds(k_scan<W, false>, lds);
-      hipLaunchKernelGGL((k_scan<W, false>), dim3(sgrid), dim3(wpb * kWave), lds, stream, sp);
+      if (recv) {  // exchange mode, keys first: the runs + the received keys' CAS inserts
+        MG_ENSURE(d_rdst, rdst_cap, run_cap * nreg);
+        sp.run_dst = ctx->d_rdst;
+        ctx->runs_meta8 = true;
+        sp.recv_keys = ctx->rk_keys;
+        sp.recv_cnt = ctx->rk_cnt;
+        sp.recv_slot = ctx->rk_slot;
+        sp.recv_total = ctx->rk_total;
+        sp.recv_P = ctx->nranks;
+        sp.cell_lo = ctx->cell_lo;
+      }
+      bool masks = false;
+      if constexpr (W <= 8) masks = scan_masks(ctx);
+      if constexpr (W <= 8) {
+        if (masks) launch_k<true>(ctx, index, recv, G > 1, sgrid, wpb, lds, stream, sp);
+      }
+      if (!masks) launch_k<false>(ctx, index, recv, G > 1, sgrid, wpb, lds, stream, sp);
     }
     (void)hipEventRecord(ctx->ev[7], stream);
     return hipGetLastError() == hipSuccess ? 0 : -1;
@@ -4236,6 +4385,7 @@ int mg_set_option(mg_ctx* ctx, const char* name, int64_t value) {
   if (flag("stats", &ctx->stats) || flag("halving", &ctx->halving_low) || flag("layout", &ctx->layout) ||
       flag("contain_jcut", &ctx->contain_jcut) || flag("contain_skip", &ctx->contain_skip) ||
       flag("contain_prune", &ctx->contain_prune) || flag("cells_double", &ctx->cells_double) || flag("probe_share", &ctx->probe_share) ||
+      flag("run_masks", &ctx->run_masks) ||
       flag("probe_compact", &ctx->probe_compact) || flag("live_index", &ctx->live_index) ||
       flag("xchg_sort_runs", &ctx->xchg_sort_runs) || flag("layout_scratch", &ctx->layout_scratch) ||
       flag("xchg_windows", &ctx->xchg_windows) || flag("chain_par", &ctx->chain_par) ||
