@@ -335,6 +335,25 @@ class OverlapGraph {
   void calculateCoverageOfAllEdges();
   // Until this is called the environment variable MG_DEVICE_PLACES decides (0 = host mirrors).
   static void setDevicePlacements(bool on);
+  // findSupportByMatepairsAndMerge (:1892-2002): every mate entry's bounded
+  // search between its two reads' edges (findPathBetweenMatepairs), the list of
+  // supported edge pairs, then the merge of every pair with support >= 3 in
+  // the order of the reference's sort; returns the number of pairs merged, and
+  // 0 at once when there is no paired-end file (:1897).  Needs
+  // calculateMeanAndSdOfInsertSize first (main.cpp:59 before :71).  The search
+  // runs in one device call (mg_mate_paths; contexts as above) and the host
+  // mirror (mg::mate_paths) finishes the entries the device deferred; without
+  // a HIP device, or with device paths off, the mirror searches them all.  The
+  // same graph either way.  The reference's cout lines are not printed here (mg_overlap
+  // -support prints the counts); the three counters are kept.
+  UINT64 findSupportByMatepairsAndMerge();
+  UINT64 getNoPathsFound() const { return pathCounters[0]; }
+  UINT64 getPathsFound() const { return pathCounters[1]; }
+  UINT64 getMatepairsOnSameEdge() const { return pathCounters[2]; }
+  // not in the reference: the size of listOfPairedEdges ("... merged out of N")
+  UINT64 getNumberOfPairedEdges() const { return pathCounters[3]; }
+  // Until this is called the environment variable MG_DEVICE_PATHS decides (0 = host mirror).
+  static void setDevicePaths(bool on);
   const mg_timings& timings() const { return lastTimings; }
 
  private:
@@ -343,6 +362,7 @@ class OverlapGraph {
   std::vector<std::vector<Edge*>*>* graph = nullptr;
   UINT64 numberOfNodes = 0, numberOfEdges = 0;
   std::vector<UINT64> meanOfInsertSizes, sdOfInsertSizes, numberOfInsertSizes;  // OverlapGraph.h:38-39
+  UINT64 pathCounters[4] = {0, 0, 0, 0};  // noPathsFound, pathsFound, mpOnSameEdge, paired edges
   bool containedDone = false;
   mg_timings lastTimings{};
   mg::UnitigGraph* unitig = nullptr;  // the list state the contraction steps work on

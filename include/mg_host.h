@@ -286,6 +286,48 @@ void mgh_mean_sd(uint64_t count, uint64_t sum, uint64_t sumsq, uint64_t* mean, u
 uint64_t mgh_graph_read_locations(const mgh_graph* g, uint64_t* n_reads, uint64_t* start, mg_place* out,
                                   uint64_t cap);
 
+/* --- mate-pair path support: findSupportByMatepairsAndMerge (OverlapGraph.cpp:1892-2002)
+ * with findPathBetweenMatepairs (:1645-1730) and exploreGraph (:1781-1870).  The
+ * definitions are in include/mg_overlap.h ("mate-pair path support"). */
+/* twin[k] = the index of edge k's reverse edge, both in
+ * mgh_graph_contig_edges(all = 1) order.  Returns the number of edges; entries
+ * beyond cap are not written. */
+uint64_t mgh_graph_edge_twins(const mgh_graph* g, uint32_t* twin, uint64_t cap);
+/* mgh_graph_read_locations in the reference's list order: per read its forward
+ * list (listOfEdgesForward / locationOnEdgeForward) in list order, then its
+ * reverse list in list order -- the order findPathBetweenMatepairs walks. */
+uint64_t mgh_graph_location_lists(const mgh_graph* g, uint64_t* n_reads, uint64_t* start, mg_place* out,
+                                  uint64_t cap);
+/* The host mirror of mg_mate_paths + mg_copy_mate_paths + mg_copy_path_pairs
+ * over the same arrays (mg::mate_paths, mg::path_pairs), with the same -2
+ * errors.  budget = work units per entry (0 = no limit; an entry above it is
+ * MG_PATH_DEFERRED).  prior_* (all or none): the entries a device run over the
+ * same input copied out; only its MG_PATH_DEFERRED entries are searched, the
+ * others are taken as they are, so the result is the undeferred one.  status /
+ * visits: one per mate entry; path_start: one more; path / flags: written only
+ * when path_cap >= *n_path; pairs: written only when pair_cap >= *n_pairs;
+ * counters[3] = noPathsFound, pathsFound, mpOnSameEdge.  Any output may be
+ * NULL.  0 = ok; -1 = bad arguments; -2 = see mg_mate_paths. */
+int mgh_mate_paths(uint64_t n_reads, const mg_contig_edge* edges, const uint32_t* twin, uint64_t n_edges,
+                   const uint64_t* place_start, const mg_place* places, const uint64_t* mate_start,
+                   const mg_mate* mates, const uint64_t* mean, const uint64_t* sd, uint32_t n_datasets,
+                   uint64_t budget, const uint8_t* prior_status, const uint32_t* prior_visits,
+                   const uint64_t* prior_start, const uint32_t* prior_path, const uint8_t* prior_flags,
+                   uint8_t* status, uint32_t* visits, uint64_t* path_start, uint32_t* path, uint8_t* flags,
+                   uint64_t path_cap, uint64_t* n_path, mg_pair_support* pairs, uint64_t pair_cap, uint64_t* n_pairs,
+                   uint64_t* counters, char* err, uint64_t err_cap);
+/* The second half (:1968-1992) on a contracted or re-read handle: std::sort of
+ * the records by support (descending, pairedEdges::operator<), in the order
+ * given, then mergeEdges of every pair that no earlier merge freed and whose
+ * support is >= min_support (the reference: minimumSupport = 3).  The pairs'
+ * edges index mgh_graph_contig_edges(all = 1) of the handle as it is now.
+ * *merged = pairsOfEdgesMerged.  0 = ok; -1 = bad arguments; -4 = an
+ * orientation pair mergeEdges rejects; -5 = a pair that would be merged is one
+ * edge twice or an edge and its twin (the reference touches a removed edge
+ * there): err names it and the graph is unchanged. */
+int mgh_graph_merge_supported(mgh_graph* g, const mg_pair_support* pairs, uint64_t n, uint64_t min_support,
+                              uint64_t* merged, char* err, uint64_t err_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -389,6 +389,101 @@ int mg_insert_sizes(mg_ctx* ctx, const uint64_t* mate_start, const mg_mate* mate
  * entry) and no result is written. */
 int mg_edge_coverage(mg_ctx* ctx, const uint32_t* freq, uint64_t* out, float* device_ms);
 
+/* --- mate-pair path support: the scoring half of findSupportByMatepairsAndMerge
+ * (OverlapGraph.cpp:1892-1966) with findPathBetweenMatepairs (:1645-1730) and
+ * exploreGraph (:1781-1870), one lane per mate entry.
+ *
+ * INPUTS.  edges: every directed edge once, in mgh_graph_contig_edges(all = 1)
+ * order (u order, each graph[u] in list order), so src never decreases, the
+ * edges of one source are contiguous and their order is the order exploreGraph
+ * walks (:1863); only src, dst, offset and orient are read.  twin[k]: the index
+ * of edge k's reverse edge (mgh_graph_edge_twins).  Placements: a CSR over read
+ * IDs (n_reads + 2 starts) of mg_place records; a read's forward list is its
+ * records with flags bit 0 set, in CSR order, its reverse list the others, in
+ * CSR order.  mgh_graph_location_lists gives the reference's list order (the
+ * order loc_fwd / loc_rev keep); place_start = NULL takes the resident
+ * placements of mg_build_placements, which hold the same SET in (edge,
+ * position) order: the order of the combos decides which path is "first", so
+ * the supported set of an entry is the same, but which of two equal adjacent
+ * pairs of a path carries the flag, and so a pair's multiplicity, can differ
+ * when a path repeats an adjacent pair.  Mates: a CSR in mg_copy_mate_pairs'
+ * layout, or NULL: the resident lists.  mean[d], sd[d] per dataset.
+ *
+ * PER MATE ENTRY t = (A, j) holding (B, orient, d), t ascending in (A, j):
+ *   skipped (MG_PATH_SKIPPED): A > B (A = B is processed) or mean[d] == 0.
+ *   A's list is its forward list iff orient is 2 or 3, B's iff orient is 0 or 2.
+ *   same edge (MG_PATH_SAME_EDGE): either list is empty (:1667 returns false
+ *     too), or some (i, j) has first == last or first == twin[last].
+ *   otherwise the combos (i, j), i-major: d1 = offset(first) - loc1[i], d2 =
+ *     loc2[j]; explored iff d1 + d2 < mean + 3 sd.  All arithmetic is unsigned
+ *     64-bit and wraps; with 3 sd > mean the bound mean - 3 sd wraps and no
+ *     destination is ever in range.
+ *   exploreGraph: level 0 holds (first, d1).  A child of the edge at `level` is
+ *     an edge c of graph[dst] in list order with matchEdgeType(edge, c) and
+ *     len[level] < mean + 3 sd.  At level + 1 > 100 the child returns at once (a
+ *     path has at most 101 edges).  c == last with d2 + len[level] in [mean -
+ *     3 sd, mean + 3 sd] (both inclusive) ends a path there without descending;
+ *     any other child (an out-of-range arrival at `last` too) is pushed with
+ *     len = offset(c) + len[level] and walked through.  The first path of a
+ *     combo is kept with all flags 1; every later path of that combo clears the
+ *     flag of each adjacent pair of the first path that is not adjacent in it.
+ *   across combos: the first combo that finds a path gives the entry's path
+ *     and flags; every later successful combo clears flag k unless (path[k],
+ *     path[k + 1]) is adjacent in its own first path at a position whose flag
+ *     is 1.
+ *   status MG_PATH_NONE (no combo found a path) or MG_PATH_FOUND (path, flags).
+ * WORK UNITS of an entry: one per (i, j) of the same-edge test, one per child
+ * looked at, one per first-path position compared when a later path arrives and
+ * one per kept-path position compared when a later combo succeeds.  An entry
+ * whose units exceed option "path_budget" (default 2^16) is MG_PATH_DEFERRED
+ * and leaves no partial result: the reference's search has no limit, a kernel
+ * has.  mgh_mate_paths finishes deferred entries exactly (its `prior`).
+ *
+ * AGGREGATE: listOfPairedEdges before :1968.  Over the entries in t order and
+ * k ascending, every flagged pair (a, b) = (path[k], path[k + 1]) is dropped if
+ * a and b are both self-loops, else joins the record that holds (a, b) or
+ * (twin[b], twin[a]), else opens a record with the orientation first seen.
+ * Records (edge1, edge2, support) come in first-seen order.  counters[3] =
+ * noPathsFound, pathsFound, mpOnSameEdge (:1901).
+ *
+ * mg_mate_paths: a validation pass first, so nothing indexes with an unchecked
+ * value: -2 with mg_last_error naming the first offender, in this order: an
+ * edge whose src is below its predecessor's, a twin outside the edges, a
+ * placement whose edge is outside the edges, a mate entry whose owner or mate
+ * ID lies outside 1..n_reads or whose dataset is not below n_datasets.  Then
+ * the entries are explored in batches of option "path_batch" lanes (default
+ * 2^18) over a level-major workspace, and aggregated: flagged positions
+ * compacted by a scan, a stable radix sort by canonical key min((a, b),
+ * (twin[b], twin[a])), run heads (first position, run length = support), and a
+ * sort of the heads by first position.  With deferred entries (*n_deferred >
+ * 0) counters and pairs cover the other entries only; the caller finishes with
+ * mgh_mate_paths over the copied entries.  n_reads must equal the resident
+ * read count when a resident CSR is taken; with two caller CSRs the context
+ * needs no reads.  -1: bad arguments, a malformed CSR, a sharded or
+ * exchange-mode context, 2^31 or more edges, entries or path positions. */
+enum { MG_PATH_SKIPPED = 0, MG_PATH_SAME_EDGE = 1, MG_PATH_NONE = 2, MG_PATH_FOUND = 3, MG_PATH_DEFERRED = 4 };
+typedef struct mg_pair_support {
+  uint32_t edge1, edge2; /* indices into edges, in the orientation first seen */
+  uint64_t support;
+} mg_pair_support;
+int mg_mate_paths(mg_ctx* ctx, const mg_contig_edge* edges, const uint32_t* twin, uint64_t n_edges, uint64_t n_reads,
+                  const uint64_t* place_start, const mg_place* places, const uint64_t* mate_start,
+                  const mg_mate* mates, const uint64_t* mean, const uint64_t* sd, uint32_t n_datasets,
+                  uint64_t* counters, uint64_t* n_pairs, uint64_t* n_deferred, float* device_ms);
+/* Sizes and times of the last mg_mate_paths: out[4] = mate entries, path
+ * positions, pairs, deferred entries; ms[2] = the explore kernels, the
+ * aggregate (device time by events).  Either may be NULL. */
+int mg_mate_paths_info(mg_ctx* ctx, uint64_t* out, float* ms);
+/* Per-entry results: status and visits (work units; of a deferred entry, those
+ * spent before it gave up) have one entry per mate entry, path_start one more;
+ * path / flags (path_cap positions, written only when path_cap >= the total):
+ * entry t's path = path[path_start[t] .. path_start[t + 1]), flags[p] = 1 when
+ * (path[p], path[p + 1]) is supported (0 at a path's last position).  Any
+ * pointer may be NULL. */
+int mg_copy_mate_paths(mg_ctx* ctx, uint8_t* status, uint32_t* visits, uint64_t* path_start, uint32_t* path,
+                       uint8_t* flags, uint64_t path_cap);
+int mg_copy_path_pairs(mg_ctx* ctx, mg_pair_support* out, uint64_t cap, uint64_t* n_copied);
+
 /* --- sharding (multi-GPU, one process per GPU) ---------------------------- */
 /* Restrict this context to index buckets owned by `rank` of `nranks`
  * (bucket-range sharding) and/or to the source reads with
@@ -609,6 +704,11 @@ int mg_get_counters(const mg_ctx* ctx, mg_counters* c);
  *                   ends); longer lists take the segmented radix sort;
  *  "cov_budget"     tests: per-base counters one chunk of mg_edge_coverage holds
  *                   (0 = default 2^25); an edge above it is a chunk of its own;
+ *  "path_batch"     mate entries one explore launch of mg_mate_paths takes (0 = default
+ *                   2^18; its workspace is 2,626 B per entry of a batch);
+ *  "path_budget"    work units one mate entry of mg_mate_paths may spend before it is
+ *                   deferred to the host mirror (0 = default 2^16): the one option a
+ *                   call's own output depends on; the finished result does not;
  *  "phase_limit", "max_blocks"
  *                   diagnostics: stop the probe after a phase / cap its grid. */
 int mg_set_option(mg_ctx* ctx, const char* name, int64_t value);

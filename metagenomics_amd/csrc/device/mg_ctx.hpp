@@ -169,6 +169,27 @@ struct PlaceStage {
   EventPair ev;
 };
 
+// mate-pair paths (mg_paths.hip, mg_mate_paths): per mate entry its status,
+// work units and path, the paths of all entries end to end ("path space",
+// entry t at pstart[t]) with one flag per position, and the supported pairs.
+// ready until the next mg_mate_paths
+struct PathStage {
+  bool ready = false;
+  uint64_t n_entries = 0, n_path = 0, n_pairs = 0, n_deferred = 0;
+  DevArray<uint8_t> status;   // per entry: MG_PATH_*
+  DevArray<uint32_t> visits;  // per entry: work units spent
+  DevArray<uint64_t> plen;    // per entry (+ 1): edges in its path (scan input)
+  DevArray<uint64_t> pstart;  // per entry (+ 1): where its path starts
+  DevArray<uint32_t> path;    // path space: edge indices
+  DevArray<uint8_t> flags;    // path space: 1 = (path[p], path[p + 1]) is supported
+  DevArray<mg_pair_support> pairs;
+  // options "path_batch" (mate entries per explore launch, 0 = 2^18) and
+  // "path_budget" (work units per mate entry, 0 = 2^16)
+  uint64_t batch = 0, budget = 0;
+  float explore_ms = 0.f, aggregate_ms = 0.f;
+  EventPair ev;
+};
+
 struct mg_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -475,6 +496,7 @@ struct mg_ctx {
   MateStage mates;
   ContigStage contigs;
   PlaceStage places;
+  PathStage paths;
 };
 
 #define MG_TRY(expr)                                                                  \

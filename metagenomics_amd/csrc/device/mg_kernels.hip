@@ -4377,6 +4377,14 @@ int mg_set_option(mg_ctx* ctx, const char* name, int64_t value) {
     ctx->places.cov_budget = (uint64_t)std::max<int64_t>(0, value);
     return 0;
   }
+  if (!strcmp(name, "path_batch")) {  // mate entries per explore launch of mg_mate_paths (0 = default)
+    ctx->paths.batch = (uint64_t)std::max<int64_t>(0, value);
+    return 0;
+  }
+  if (!strcmp(name, "path_budget")) {  // work units per mate entry of mg_mate_paths (0 = default)
+    ctx->paths.budget = (uint64_t)std::max<int64_t>(0, value);
+    return 0;
+  }
   if (!strcmp(name, "run_cap")) {  // tests: initial run records per scan region (0 = sized from the reads)
     ctx->run_cap_opt = (uint64_t)std::max<int64_t>(0, value);
     ctx->run_cap_need = 0;

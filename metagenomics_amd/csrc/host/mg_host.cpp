@@ -20,6 +20,7 @@
 #include "mg_contigs.hpp"
 #include "mg_mates.hpp"
 #include "mg_parse.hpp"
+#include "mg_paths.hpp"
 #include "mg_places.hpp"
 #include "mg_unitig.hpp"
 #include "mg_graph.hpp"
@@ -875,6 +876,115 @@ bool OverlapGraph::calculateMeanAndSdOfInsertSize() {
     numberOfInsertSizes[d] = sums[3 * d];
   }
   return true;
+}
+
+namespace {
+// g_device_paths: OverlapGraph::setDevicePaths; -1 = not called, the
+// environment variable MG_DEVICE_PATHS decides (unset: device)
+int g_device_paths = -1;
+
+bool use_device_paths(UINT64 n_reads) {
+  const char* v = std::getenv("MG_DEVICE_PATHS");
+  const bool on = g_device_paths < 0 ? (v && *v ? std::atoi(v) != 0 : true) : g_device_paths != 0;
+  return on && n_reads && mg_device_count() > 0;
+}
+}  // namespace
+
+void OverlapGraph::setDevicePaths(bool on) { g_device_paths = on ? 1 : 0; }
+
+UINT64 OverlapGraph::findSupportByMatepairsAndMerge() {
+  const char* who = "findSupportByMatepairsAndMerge";
+  if (!dataSet) throw mg::Error(std::string(who) + ": no Dataset");
+  pathCounters[0] = pathCounters[1] = pathCounters[2] = pathCounters[3] = 0;
+  const uint32_t D = (uint32_t)dataSet->pairedEndDatasetFileNames.size();
+  if (D == 0) return 0;  // :1897
+  adoptEdgeLists();
+  if (!unitig) throw mg::Error(std::string(who) + ": no replayed graph");
+  if (meanOfInsertSizes.size() != D || sdOfInsertSizes.size() != D)
+    throw mg::Error(std::string(who) + ": calculateMeanAndSdOfInsertSize must run first");
+  const UINT64 N = dataSet->getNumberOfUniqueReads();
+  if (!unitig->track || unitig->loc_fwd.size() != N + 1 || unitig->loc_rev.size() != N + 1)
+    throw mg::Error(std::string(who) + ": the graph keeps no read locations");
+  // the edges, their twins and the location lists in list order, as mgh_graph_edge_twins / _location_lists give them
+  mg::ContigLists c;
+  mg::contig_edges(*unitig, true, &c);
+  std::vector<uint32_t> index(unitig->pool.size(), 0xFFFFFFFFu);
+  for (size_t k = 0; k < c.pool.size(); ++k) index[c.pool[k]] = (uint32_t)k;
+  std::vector<uint32_t> twin(c.pool.size());
+  for (size_t k = 0; k < c.pool.size(); ++k) twin[k] = index[unitig->pool[c.pool[k]].rev];
+  std::vector<uint64_t> pstart(N + 2, 0);
+  std::vector<mg_place> places;
+  for (UINT64 r = 1; r <= N; ++r) {
+    pstart[r] = places.size();
+    for (int side = 0; side < 2; ++side)
+      for (const mg::ReadLoc& l : side ? unitig->loc_rev[r] : unitig->loc_fwd[r])
+        places.push_back(mg_place{index[l.edge], side ? 0u : 1u, l.loc});
+  }
+  pstart[N + 1] = places.size();
+  std::vector<uint64_t> mstart(N + 2, 0);
+  std::vector<mg_mate> mates(dataSet->mates.size());
+  if (dataSet->mateStart.size() == N + 2) mstart = dataSet->mateStart;
+  else mates.clear();
+  for (size_t i = 0; i < mates.size(); ++i)
+    mates[i] = mg_mate{(uint32_t)dataSet->mates[i].matePairID, dataSet->mates[i].matePairOrientation,
+                       dataSet->mates[i].datasetNumber, 0};
+  const std::vector<uint64_t> mean(meanOfInsertSizes.begin(), meanOfInsertSizes.end());
+  const std::vector<uint64_t> sd(sdOfInsertSizes.begin(), sdOfInsertSizes.end());
+  mg::PathInput in;
+  in.n_reads = N;
+  in.edges = c.edges.data();
+  in.twin = twin.data();
+  in.n_edges = c.edges.size();
+  in.place_start = pstart.data();
+  in.places = places.data();
+  in.mate_start = mstart.data();
+  in.mates = mates.data();
+  in.mean = mean.data();
+  in.sd = sd.data();
+  in.n_datasets = D;
+  std::string err;
+  if (mg::paths_validate(in, &err)) throw mg::Error(std::string(who) + ": " + err);
+  std::vector<mg_pair_support> pairs;
+  uint64_t counters[3] = {0, 0, 0};
+  mg::PathEntries prior, res;
+  bool have_pairs = false, have_prior = false;
+  if (use_device_paths(N)) {
+    PlaceCtx pc(hashTable, dataSet, who);
+    uint64_t n_pairs = 0, n_deferred = 0, info[4] = {0, 0, 0, 0}, copied = 0;
+    if (mg_mate_paths(pc.ctx, in.edges, in.twin, in.n_edges, N, in.place_start, in.places, in.mate_start, in.mates,
+                      in.mean, in.sd, D, counters, &n_pairs, &n_deferred, nullptr))
+      throw mg::Error(std::string(who) + ": " + mg_last_error(pc.ctx));
+    if (n_deferred == 0) {
+      pairs.resize(n_pairs);
+      if (mg_copy_path_pairs(pc.ctx, pairs.data(), n_pairs, &copied) || copied != n_pairs)
+        throw mg::Error(std::string(who) + ": " + mg_last_error(pc.ctx));
+      have_pairs = true;
+    } else {  // the mirror searches the deferred entries and rebuilds the list over all of them
+      if (mg_mate_paths_info(pc.ctx, info, nullptr)) throw mg::Error(std::string(who) + ": " + mg_last_error(pc.ctx));
+      prior.status.resize(info[0]);
+      prior.visits.resize(info[0]);
+      prior.start.resize(info[0] + 1);
+      prior.path.resize(info[1]);
+      prior.flags.resize(info[1]);
+      if (mg_copy_mate_paths(pc.ctx, prior.status.data(), prior.visits.data(), prior.start.data(), prior.path.data(),
+                             prior.flags.data(), info[1]))
+        throw mg::Error(std::string(who) + ": " + mg_last_error(pc.ctx));
+      have_prior = true;
+    }
+  }
+  if (!have_pairs) {
+    if (mg::mate_paths(in, 0, have_prior ? &prior : nullptr, &res, &err)) throw mg::Error(std::string(who) + ": " + err);
+    mg::path_pairs(in, res, &pairs, counters);
+  }
+  uint64_t merged = 0;
+  if (mg::merge_supported(unitig, c.pool, pairs.data(), pairs.size(), 3, &merged, &err))
+    throw mg::Error(std::string(who) + ": " + err);
+  pathCounters[0] = counters[0];
+  pathCounters[1] = counters[1];
+  pathCounters[2] = counters[2];
+  pathCounters[3] = pairs.size();
+  materialize();
+  return merged;
 }
 
 void OverlapGraph::getBaseByBaseCoverage(Edge* edge) {
@@ -1828,6 +1938,144 @@ uint64_t mgh_graph_read_locations(const mgh_graph* g, uint64_t* n_reads_out, uin
     return total;
   } catch (const std::exception&) {
     return 0;
+  }
+}
+
+namespace {
+// every edge of the lists -> its index in contig_edges(all) order, and back
+void edge_indices(const mg::UnitigGraph& u, std::vector<uint32_t>* pool_of, std::vector<uint32_t>* index) {
+  mg::ContigLists c;
+  mg::contig_edges(u, true, &c);
+  *pool_of = c.pool;
+  index->assign(u.pool.size(), 0xFFFFFFFFu);
+  for (size_t k = 0; k < c.pool.size(); ++k) (*index)[c.pool[k]] = (uint32_t)k;
+}
+}  // namespace
+
+uint64_t mgh_graph_edge_twins(const mgh_graph* g, uint32_t* twin, uint64_t cap) {
+  if (!g || !g->u) return 0;
+  try {
+    std::vector<uint32_t> pool_of, index;
+    edge_indices(*g->u, &pool_of, &index);
+    for (size_t k = 0; k < pool_of.size() && k < cap; ++k)
+      if (twin) twin[k] = index[g->u->pool[pool_of[k]].rev];
+    return pool_of.size();
+  } catch (const std::exception&) {
+    return 0;
+  }
+}
+
+uint64_t mgh_graph_location_lists(const mgh_graph* g, uint64_t* n_reads_out, uint64_t* start, mg_place* out,
+                                  uint64_t cap) {
+  if (n_reads_out) *n_reads_out = 0;
+  if (!g || !g->u || !g->u->track || g->u->loc_fwd.empty()) return 0;
+  try {
+    const mg::UnitigGraph& u = *g->u;
+    std::vector<uint32_t> pool_of, index;
+    edge_indices(u, &pool_of, &index);
+    const uint64_t n_reads = u.loc_fwd.size() - 1;
+    if (n_reads_out) *n_reads_out = n_reads;
+    uint64_t total = 0;
+    if (start) start[0] = start[1] = 0;
+    for (uint64_t r = 1; r <= n_reads; ++r) {
+      if (start) start[r] = total;
+      for (int side = 0; side < 2; ++side)
+        for (const mg::ReadLoc& l : side ? u.loc_rev[r] : u.loc_fwd[r]) {
+          if (out && total < cap) out[total] = mg_place{index[l.edge], side ? 0u : 1u, l.loc};
+          ++total;
+        }
+    }
+    if (start) start[n_reads + 1] = total;
+    return total;
+  } catch (const std::exception&) {
+    return 0;
+  }
+}
+
+int mgh_mate_paths(uint64_t n_reads, const mg_contig_edge* edges, const uint32_t* twin, uint64_t n_edges,
+                   const uint64_t* place_start, const mg_place* places, const uint64_t* mate_start,
+                   const mg_mate* mates, const uint64_t* mean, const uint64_t* sd, uint32_t n_datasets,
+                   uint64_t budget, const uint8_t* prior_status, const uint32_t* prior_visits,
+                   const uint64_t* prior_start, const uint32_t* prior_path, const uint8_t* prior_flags,
+                   uint8_t* status, uint32_t* visits, uint64_t* path_start, uint32_t* path, uint8_t* flags,
+                   uint64_t path_cap, uint64_t* n_path, mg_pair_support* pairs, uint64_t pair_cap, uint64_t* n_pairs,
+                   uint64_t* counters, char* err, uint64_t err_cap) {
+  put_err("", err, err_cap);
+  if (n_path) *n_path = 0;
+  if (n_pairs) *n_pairs = 0;
+  try {
+    mg::PathInput in;
+    in.n_reads = n_reads;
+    in.edges = edges;
+    in.twin = twin;
+    in.n_edges = n_edges;
+    in.place_start = place_start;
+    in.places = places;
+    in.mate_start = mate_start;
+    in.mates = mates;
+    in.mean = mean;
+    in.sd = sd;
+    in.n_datasets = n_datasets;
+    std::string e;
+    int rc = mg::paths_validate(in, &e);
+    if (rc) {
+      put_err(e, err, err_cap);
+      return rc;
+    }
+    const uint64_t M = mate_start[n_reads + 1];
+    mg::PathEntries prior, res;
+    const bool has_prior = prior_status || prior_visits || prior_start || prior_path || prior_flags;
+    if (has_prior) {
+      if (!prior_start || (M && (!prior_status || !prior_visits))) return -1;
+      for (uint64_t m = 0; m < M; ++m)
+        if (prior_start[m + 1] < prior_start[m]) return -1;
+      const uint64_t np = prior_start[M];
+      if (prior_start[0] != 0 || (np && (!prior_path || !prior_flags))) return -1;
+      prior.status.assign(prior_status, prior_status + M);
+      prior.visits.assign(prior_visits, prior_visits + M);
+      prior.start.assign(prior_start, prior_start + M + 1);
+      prior.path.assign(prior_path, prior_path + np);
+      prior.flags.assign(prior_flags, prior_flags + np);
+      for (uint32_t x : prior.path)
+        if (x >= n_edges) return -1;
+    }
+    rc = mg::mate_paths(in, budget, has_prior ? &prior : nullptr, &res, &e);
+    if (rc) {
+      put_err(e, err, err_cap);
+      return rc;
+    }
+    std::vector<mg_pair_support> pr;
+    uint64_t cnt[3];
+    mg::path_pairs(in, res, &pr, cnt);
+    if (status) std::copy(res.status.begin(), res.status.end(), status);
+    if (visits) std::copy(res.visits.begin(), res.visits.end(), visits);
+    if (path_start) std::copy(res.start.begin(), res.start.end(), path_start);
+    if (path && path_cap >= res.path.size()) std::copy(res.path.begin(), res.path.end(), path);
+    if (flags && path_cap >= res.flags.size()) std::copy(res.flags.begin(), res.flags.end(), flags);
+    if (n_path) *n_path = res.path.size();
+    if (pairs && pair_cap >= pr.size()) std::copy(pr.begin(), pr.end(), pairs);
+    if (n_pairs) *n_pairs = pr.size();
+    if (counters) std::copy(cnt, cnt + 3, counters);
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_graph_merge_supported(mgh_graph* g, const mg_pair_support* pairs, uint64_t n, uint64_t min_support,
+                              uint64_t* merged, char* err, uint64_t err_cap) {
+  put_err("", err, err_cap);
+  if (merged) *merged = 0;
+  if (!g || !g->u) return -1;
+  try {
+    std::vector<uint32_t> pool_of, index;
+    edge_indices(*g->u, &pool_of, &index);
+    std::string e;
+    const int rc = mg::merge_supported(g->u.get(), pool_of, pairs, n, min_support, merged, &e);
+    if (rc) put_err(e, err, err_cap);
+    return rc;
+  } catch (const std::exception&) {
+    return -1;
   }
 }
 

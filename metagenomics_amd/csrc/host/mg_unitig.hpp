@@ -52,6 +52,9 @@ class UnitigGraph {
   uint64_t contract_composite_paths();  // :669-696
   uint64_t remove_dead_end_nodes();     // :931-988
   void sort_edges();                    // :2799-2808
+  // mergeEdges (:702-753) of two pool entries, for findSupportByMatepairsAndMerge's
+  // loop (mg_paths.cpp); sets bad_merge on an orientation pair it rejects
+  void merge_edges(uint32_t e1, uint32_t e2) { merge(e1, e2); }
   // saveGraphToFile (:1219-1261); 0 ok, -1 open/write failure
   int save_unitig(const char* path) const;
   // every list in list order as "u v orient offset nreads r:o:d ..." rows,

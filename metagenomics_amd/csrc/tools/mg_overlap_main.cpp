@@ -26,6 +26,12 @@
 //                (MG_DEVICE_CONTIGS=0 or no device: by the host mirror), and
 //                getStringInEdge of every edge of every list in list order as
 //                "src dst orient offset nreads string" lines to <prefix>.estrings;
+//   -support     main.cpp:59 and :71: calculateMeanAndSdOfInsertSize (without -insert's
+//                lines and coverage), then findSupportByMatepairsAndMerge; prints the
+//                reference's six summary lines (pairs merged out of the supported
+//                pairs, the three counters and their sums) and writes the graph
+//                after the merge to <prefix>.support.unitig (MG_DEVICE_PATHS=0 or no
+//                device: the search by the host mirror);
 //   -insert      main.cpp:59's calculateMeanAndSdOfInsertSize after the .unitig (also
 //                after -s), for use with -pe: per dataset the reference's three
 //                stdout lines ("Mean set to: ", "SD set to: ", "Reads on same
@@ -304,9 +310,27 @@ static void save_insert(OverlapGraph* g, Dataset* ds, size_t n_pe, const std::st
   std::fclose(f);
 }
 
+// main.cpp:71's findSupportByMatepairsAndMerge with the reference's summary lines (:1994-2000; its
+// "Merging" lines are not reproduced), then the graph after the merge
+static void save_support(OverlapGraph* g, size_t n_pe, const std::string& prefix) {
+  g->calculateMeanAndSdOfInsertSize();  // main.cpp:59 (again after -insert, whose coverage pass this does not need)
+  const UINT64 merged = g->findSupportByMatepairsAndMerge();
+  const UINT64 none = g->getNoPathsFound(), found = g->getPathsFound(), same = g->getMatepairsOnSameEdge();
+  if (n_pe) {  // (:1897 returns before any line)
+    std::printf("%llu Pairs of Edges merged out of %llu supported pairs of edges\n", (unsigned long long)merged,
+                (unsigned long long)g->getNumberOfPairedEdges());
+    std::printf("No paths found between %llu matepairs that are on different edge.\n", (unsigned long long)none);
+    std::printf("Paths found between %llu matepairs that are on different edge.\n", (unsigned long long)found);
+    std::printf("Total matepairs on different edges %llu\n", (unsigned long long)(none + found));
+    std::printf("Total matepairs on same edge %llu\n", (unsigned long long)same);
+    std::printf("Total matepairs %llu\n", (unsigned long long)(none + found + same));
+  }
+  g->saveGraphToFile(prefix + ".support.unitig");
+}
+
 static void usage() {
   std::fprintf(stderr,
-               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-contigs] [-insert] [-nocontract | -raw | -s | -xchg K "
+               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-contigs] [-insert] [-support] [-nocontract | -raw | -s | -xchg K "
                "[-xchg-sim P] [-xchg-caps F]]\n");
 }
 
@@ -315,7 +339,7 @@ int main(int argc, char** argv) {
   std::string prefix;
   unsigned long long l = 0;
   int k = 0, dev = 0;
-  bool raw = false, nocontract = false, resume = false, mates = false, contigs = false, insert = false;
+  bool raw = false, nocontract = false, resume = false, mates = false, contigs = false, insert = false, support = false;
   int xchg_steps = -1, xchg_sim = 0;
   double xchg_caps = 1.0;
   for (int i = 1; i < argc; ++i) {
@@ -343,6 +367,8 @@ int main(int argc, char** argv) {
       contigs = true;
     } else if (a == "-insert") {
       insert = true;
+    } else if (a == "-support") {
+      support = true;
     } else if (a == "-xchg" && i + 1 < argc) {
       xchg_steps = std::max(0, std::atoi(argv[++i]));
     } else if (a == "-xchg-sim" && i + 1 < argc) {
@@ -384,6 +410,7 @@ int main(int argc, char** argv) {
       if (mates) save_mates(ds, prefix + ".resumed.mates");
       if (contigs) save_contigs(g, ds, prefix);
       if (insert) save_insert(g, ds, pe.size(), prefix);
+      if (support) save_support(g, pe.size(), prefix);
       std::printf("{\"unique_reads\": %llu, \"nodes\": %llu, \"directed_edges\": %llu}\n",
                   (unsigned long long)ds->getNumberOfUniqueReads(), (unsigned long long)g->getNumberOfNodes(),
                   (unsigned long long)g->getNumberOfEdges());
@@ -405,6 +432,7 @@ int main(int argc, char** argv) {
       g->saveGraphToFile(prefix + ".unitig");
       if (contigs) save_contigs(g, ds, prefix);
       if (insert) save_insert(g, ds, pe.size(), prefix);
+      if (support) save_support(g, pe.size(), prefix);
     }
     const mg_timings& t = g->timings();
     std::printf(

@@ -36,6 +36,12 @@ CONTIG_EDGE_DTYPE = np.dtype({"names": ["src", "dst", "offset", "first", "n", "t
 PLACE_DTYPE = np.dtype([("edge", "<u4"), ("flags", "<u4"), ("distance", "<u8")])
 # the reference's bound on an insert size (OverlapGraph.cpp:1168)
 MAX_INSERT_DISTANCE = 1000
+# one supported pair of edges (mg_pair_support, include/mg_overlap.h): 16 bytes
+PAIR_DTYPE = np.dtype([("edge1", "<u4"), ("edge2", "<u4"), ("support", "<u8")])
+# status of a mate entry's path search (MG_PATH_*, include/mg_overlap.h)
+PATH_SKIPPED, PATH_SAME_EDGE, PATH_NONE, PATH_FOUND, PATH_DEFERRED = range(5)
+# the reference's minimumSupport (Common.h:43)
+MIN_SUPPORT = 3
 
 
 class MgError(RuntimeError):
@@ -174,6 +180,15 @@ def lib() -> C.CDLL:
         "mgh_edge_coverage": (i32, [vp, u64, vp, u64, vp, vp, vp, u64, vp, vp, C.c_char_p, u64]),
         "mgh_mean_sd": (None, [u64, u64, u64, P(u64), P(u64)]),
         "mgh_graph_read_locations": (u64, [vp, P(u64), vp, vp, u64]),
+        "mg_mate_paths": (i32, [vp, vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, u32, vp, P(u64), P(u64), P(C.c_float)]),
+        "mg_mate_paths_info": (i32, [vp, vp, vp]),
+        "mg_copy_mate_paths": (i32, [vp, vp, vp, vp, vp, vp, u64]),
+        "mg_copy_path_pairs": (i32, [vp, vp, u64, P(u64)]),
+        "mgh_graph_edge_twins": (u64, [vp, vp, u64]),
+        "mgh_graph_location_lists": (u64, [vp, P(u64), vp, vp, u64]),
+        "mgh_mate_paths": (i32, [u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                 vp, u64, P(u64), vp, u64, P(u64), vp, C.c_char_p, u64]),
+        "mgh_graph_merge_supported": (i32, [vp, vp, u64, u64, P(u64), C.c_char_p, u64]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -628,6 +643,61 @@ class OverlapEngine:
         self.coverage_ms = float(ms.value)
         return out
 
+    # --- mate-pair path support
+    def mate_paths(self, edges, twin, mean, sd, places=None, mates=None, n_reads: int | None = None) -> "PathSupport":
+        """mg_mate_paths: the scoring half of findSupportByMatepairsAndMerge
+        (OverlapGraph.cpp:1892-1966) on the device.  edges / twin as
+        UnitigGraph.contig_edges(all_edges=True) / edge_twins give them; places =
+        a (start, records) placement CSR in the reference's list order
+        (UnitigGraph.location_lists), or None: the resident placements of
+        build_placements (the same supported set; multiplicities can differ only
+        when a path repeats an adjacent pair); mates = a (start, records) mate
+        CSR, or None: the resident lists; mean / sd per dataset.  Returns the
+        device's PathSupport; entries the device deferred (option path_budget)
+        are still PATH_DEFERRED in it: PathSupport.finish() (or
+        UnitigGraph.mate_support) completes them with the host mirror.
+        paths_ms = (explore kernels, aggregate) device time."""
+        edges = np.ascontiguousarray(edges, dtype=CONTIG_EDGE_DTYPE)
+        twin = np.ascontiguousarray(twin, dtype=np.uint32)
+        mean = np.ascontiguousarray(mean, dtype=np.uint64)
+        sd = np.ascontiguousarray(sd, dtype=np.uint64)
+        if twin.shape[0] != edges.shape[0] or mean.shape != sd.shape or mean.ndim != 1:
+            raise MgError("mate_paths: one twin per edge, one mean and one sd per dataset")
+        if places is not None:
+            places = (np.ascontiguousarray(places[0], dtype=np.uint64), np.ascontiguousarray(places[1], dtype=PLACE_DTYPE))
+        if mates is not None:
+            mates = (np.ascontiguousarray(mates[0], dtype=np.uint64), np.ascontiguousarray(mates[1], dtype=MATE_DTYPE))
+        if n_reads is None:
+            n_reads = (places[0].shape[0] - 2 if places is not None else
+                       mates[0].shape[0] - 2 if mates is not None else int(lib().mg_num_reads(self._h)))
+        for csr in (places, mates):
+            if csr is not None and (csr[0].shape[0] != n_reads + 2 or int(csr[0][-1]) > csr[1].shape[0]):
+                raise MgError("mate_paths: a CSR does not fit n_reads")
+        counters = np.zeros(3, dtype=np.uint64)
+        npairs, ndef, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        self._check(lib().mg_mate_paths(self._h, _ptr(edges), _ptr(twin), edges.shape[0], n_reads,
+                                        None if places is None else _ptr(places[0]),
+                                        None if places is None else _ptr(places[1]),
+                                        None if mates is None else _ptr(mates[0]),
+                                        None if mates is None else _ptr(mates[1]), _ptr(mean), _ptr(sd), mean.shape[0],
+                                        _ptr(counters), C.byref(npairs), C.byref(ndef), C.byref(ms)), "mate_paths")
+        info, times = np.zeros(4, dtype=np.uint64), np.zeros(2, dtype=np.float32)
+        self._check(lib().mg_mate_paths_info(self._h, _ptr(info), _ptr(times)), "mate_paths_info")
+        self.paths_ms = (float(times[0]), float(times[1]))
+        m, npath = int(info[0]), int(info[1])
+        status, visits = np.zeros(m, dtype=np.uint8), np.zeros(m, dtype=np.uint32)
+        start = np.zeros(m + 1, dtype=np.uint64)
+        path, flags = np.zeros(npath, dtype=np.uint32), np.zeros(npath, dtype=np.uint8)
+        self._check(lib().mg_copy_mate_paths(self._h, _ptr(status), _ptr(visits), _ptr(start), _ptr(path), _ptr(flags),
+                                             npath), "copy_mate_paths")
+        pairs = np.zeros(npairs.value, dtype=PAIR_DTYPE)
+        got = C.c_uint64()
+        self._check(lib().mg_copy_path_pairs(self._h, _ptr(pairs), pairs.shape[0], C.byref(got)), "copy_path_pairs")
+        # the resident CSRs come back to the host only if finish() has deferred entries to search
+        return PathSupport(status, visits, start, path, flags, pairs[: got.value], counters, int(ndef.value),
+                           (n_reads, edges, twin, places if places is not None else self.placements,
+                            mates if mates is not None else self.mate_lists, mean, sd))
+
     # --- connected components of the lists, labelled on the device
     def build_components(self) -> int:
         """mg_build_components: label every read with the smallest read ID its
@@ -950,6 +1020,85 @@ def host_edge_coverage(lens: np.ndarray, freq: np.ndarray, edges, reads, offs, o
     return out
 
 
+class PathSupport:
+    """What mate_paths / host_mate_paths return: per mate entry (in (A, j)
+    order) status[t] (PATH_*), visits[t] (work units) and its path
+    path[start[t]:start[t + 1]] (edge indices) with flags (flags[p] = 1: the
+    pair (path[p], path[p + 1]) is supported); pairs[PAIR_DTYPE] in first-seen
+    order; counters = (noPathsFound, pathsFound, mpOnSameEdge); deferred = the
+    entries still PATH_DEFERRED (pairs and counters then leave them out)."""
+
+    def __init__(self, status, visits, start, path, flags, pairs, counters, deferred, inputs):
+        self.status, self.visits, self.start, self.path, self.flags = status, visits, start, path, flags
+        self.pairs, self.counters, self.deferred = pairs, tuple(int(x) for x in counters), int(deferred)
+        self._inputs = inputs
+
+    def paths(self):
+        """[(path, flags)] per mate entry, flags without the last position's 0"""
+        s = self.start
+        return [(self.path[int(s[t]):int(s[t + 1])].tolist(), self.flags[int(s[t]):max(int(s[t + 1]) - 1, int(s[t]))].tolist())
+                for t in range(self.status.shape[0])]
+
+    def finish(self) -> "PathSupport":
+        """The deferred entries searched by the host mirror without a limit and
+        spliced in at their positions: the undeferred result.  A result of
+        OverlapEngine.mate_paths over resident CSRs fetches them from its
+        engine here, so call this while that engine is open and before
+        build_placements or mate_pairs runs on it again: the fetched CSRs are
+        checked against the entry count, not against the earlier contents."""
+        if not self.deferred:
+            return self
+        inputs = [x() if callable(x) else x for x in self._inputs]  # (a resident CSR is fetched here, while its engine lives)
+        return host_mate_paths(*inputs, prior=self)
+
+
+def host_mate_paths(n_reads: int, edges, twin, places, mates, mean, sd, budget: int = 0, prior=None) -> PathSupport:
+    """mg::mate_paths + mg::path_pairs (mgh_mate_paths): the host mirror of
+    OverlapEngine.mate_paths over the same arrays; places / mates = (start,
+    records) CSRs.  budget = work units per entry (0 = no limit).  prior = a
+    PathSupport over the same input: only its PATH_DEFERRED entries are searched."""
+    edges = np.ascontiguousarray(edges, dtype=CONTIG_EDGE_DTYPE)
+    twin = np.ascontiguousarray(twin, dtype=np.uint32)
+    pstart, precs = np.ascontiguousarray(places[0], dtype=np.uint64), np.ascontiguousarray(places[1], dtype=PLACE_DTYPE)
+    mstart, mrecs = np.ascontiguousarray(mates[0], dtype=np.uint64), np.ascontiguousarray(mates[1], dtype=MATE_DTYPE)
+    mean = np.ascontiguousarray(mean, dtype=np.uint64)
+    sd = np.ascontiguousarray(sd, dtype=np.uint64)
+    if twin.shape[0] != edges.shape[0] or mean.shape != sd.shape or mean.ndim != 1 or \
+            pstart.shape[0] != n_reads + 2 or mstart.shape[0] != n_reads + 2 or \
+            int(pstart[-1]) > precs.shape[0] or int(mstart[-1]) > mrecs.shape[0]:
+        raise MgError("host_mate_paths: the arrays do not fit each other")
+    m = int(mstart[-1])
+    pr = [None] * 5
+    if prior is not None:
+        pr = [np.ascontiguousarray(prior.status, dtype=np.uint8), np.ascontiguousarray(prior.visits, dtype=np.uint32),
+              np.ascontiguousarray(prior.start, dtype=np.uint64), np.ascontiguousarray(prior.path, dtype=np.uint32),
+              np.ascontiguousarray(prior.flags, dtype=np.uint8)]
+        if pr[0].shape[0] != m or pr[1].shape[0] != m or pr[2].shape[0] != m + 1 or \
+                pr[3].shape[0] != int(pr[2][-1]) or pr[4].shape[0] != pr[3].shape[0]:
+            raise MgError("host_mate_paths: prior does not fit the mate lists")
+    status, visits = np.zeros(m, dtype=np.uint8), np.zeros(m, dtype=np.uint32)
+    start = np.zeros(m + 1, dtype=np.uint64)
+    counters = np.zeros(3, dtype=np.uint64)
+    npath, npairs = C.c_uint64(), C.c_uint64()
+    err = C.create_string_buffer(512)
+    path_cap, pair_cap = 4 * m + 1024, m + 1024
+    while True:
+        path, flags = np.zeros(path_cap, dtype=np.uint32), np.zeros(path_cap, dtype=np.uint8)
+        pairs = np.zeros(pair_cap, dtype=PAIR_DTYPE)
+        rc = lib().mgh_mate_paths(n_reads, _ptr(edges), _ptr(twin), edges.shape[0], _ptr(pstart), _ptr(precs),
+                                  _ptr(mstart), _ptr(mrecs), _ptr(mean), _ptr(sd), mean.shape[0], budget,
+                                  *(None if a is None else _ptr(a) for a in pr), _ptr(status), _ptr(visits),
+                                  _ptr(start), _ptr(path), _ptr(flags), path_cap, C.byref(npath), _ptr(pairs), pair_cap,
+                                  C.byref(npairs), _ptr(counters), err, 512)
+        if rc:
+            raise MgError(f"host_mate_paths: {err.value.decode() or 'bad arguments'} ({rc})")
+        if npath.value <= path_cap and npairs.value <= pair_cap:
+            break
+        path_cap, pair_cap = max(path_cap, npath.value), max(pair_cap, npairs.value)  # (sized now: once more)
+    return PathSupport(status, visits, start, path[: npath.value], flags[: npath.value], pairs[: npairs.value], counters,
+                       int((status == PATH_DEFERRED).sum()), (n_reads, edges, twin, (pstart, precs), (mstart, mrecs), mean, sd))
+
+
 def read_pairs(files: Sequence[str] | None = None, data: bytes | None = None):
     """The mates of every pair as storeMatePairInformation's loop reads them
     (mgh_read_pairs; `data`: one file's bytes).  Returns (text bytes, offsets
@@ -1173,6 +1322,56 @@ class UnitigGraph:
         recs = np.zeros(n, dtype=PLACE_DTYPE)
         self._L.mgh_graph_read_locations(self._g, C.byref(nr), _ptr(start), _ptr(recs), n)
         return start, recs
+
+    def location_lists(self):
+        """(start uint64[n_reads + 2], records[PLACE_DTYPE]): read_locations in
+        the reference's list order -- per read its forward list in list order,
+        then its reverse list in list order -- the order
+        findPathBetweenMatepairs walks.  None when the handle tracked none."""
+        nr = C.c_uint64(0)
+        n = int(self._L.mgh_graph_location_lists(self._g, C.byref(nr), None, None, 0))
+        if not nr.value:
+            return None
+        start = np.zeros(nr.value + 2, dtype=np.uint64)
+        recs = np.zeros(n, dtype=PLACE_DTYPE)
+        self._L.mgh_graph_location_lists(self._g, C.byref(nr), _ptr(start), _ptr(recs), n)
+        return start, recs
+
+    def edge_twins(self) -> np.ndarray:
+        """twin[k] = the index of edge k's reverse edge, both in contig_edges(all_edges=True) order"""
+        n = int(self._L.mgh_graph_edge_twins(self._g, None, 0))
+        twin = np.zeros(n, dtype=np.uint32)
+        self._L.mgh_graph_edge_twins(self._g, _ptr(twin), n)
+        return twin
+
+    def mate_support(self, mates, mean, sd, engine=None) -> PathSupport:
+        """The scoring half of findSupportByMatepairsAndMerge
+        (OverlapGraph.cpp:1892-1966) over this graph: status, paths, flags,
+        pairs and counters (PathSupport).  mates = a (start, records) mate CSR;
+        mean / sd per dataset (insert_sizes).  With an engine: the device call,
+        its deferred entries finished by the host mirror; otherwise the mirror."""
+        locs = self.location_lists()
+        if locs is None:
+            raise MgError("mate_support: the graph tracked no read locations")
+        edges = self.contig_edges(all_edges=True)[0]
+        twin = self.edge_twins()
+        if engine is not None:
+            return engine.mate_paths(edges, twin, mean, sd, places=locs, mates=mates).finish()
+        return host_mate_paths(locs[0].shape[0] - 2, edges, twin, locs, mates, mean, sd)
+
+    def merge_supported(self, pairs, min_support: int = MIN_SUPPORT) -> int:
+        """The merging half (OverlapGraph.cpp:1968-1992): std::sort of the pairs
+        by support, then mergeEdges of every pair no earlier merge freed with
+        support >= min_support.  pairs[PAIR_DTYPE] index contig_edges(all_edges=True)
+        of the graph as it is now.  Returns pairsOfEdgesMerged."""
+        pairs = np.ascontiguousarray(pairs, dtype=PAIR_DTYPE)
+        merged = C.c_uint64()
+        err = C.create_string_buffer(512)
+        rc = self._L.mgh_graph_merge_supported(self._g, _ptr(pairs), pairs.shape[0], min_support, C.byref(merged), err,
+                                               512)
+        if rc:
+            raise MgError(f"merge_supported: {err.value.decode() or 'bad arguments'} ({rc})")
+        return int(merged.value)
 
     def insert_sizes(self, mates, n_datasets: int, engine=None, max_distance: int = MAX_INSERT_DISTANCE):
         """calculateMeanAndSdOfInsertSize (OverlapGraph.cpp:1124-1211) over this

@@ -13,5 +13,5 @@ mkdir -p $B $ROOT/metagenomics_amd/lib/variants
   -I$ROOT/metagenomics_amd/csrc/device -c ${SRC:-$ROOT/metagenomics_amd/csrc/device/mg_kernels.hip} -o $B/mg_kernels.o
 O=$ROOT/metagenomics_amd/build
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -pthread -o $ROOT/metagenomics_amd/lib/variants/$NAME.so \
-  $B/mg_kernels.o $O/mg_dataset.o $O/mg_disc.o $O/mg_comp.o $O/mg_mates.o $O/mg_contigs.o $O/mg_places.o $O/mg_host.o $O/mg_graph.o \
-  $O/mg_unitig.o $O/mg_parse.o $O/mg_mates_host.o $O/mg_contigs_host.o $O/mg_places_host.o $O/mg_rdzv.o
+  $B/mg_kernels.o $O/mg_dataset.o $O/mg_disc.o $O/mg_comp.o $O/mg_mates.o $O/mg_contigs.o $O/mg_places.o $O/mg_paths.o $O/mg_host.o $O/mg_graph.o \
+  $O/mg_unitig.o $O/mg_parse.o $O/mg_mates_host.o $O/mg_contigs_host.o $O/mg_places_host.o $O/mg_paths_host.o $O/mg_rdzv.o
