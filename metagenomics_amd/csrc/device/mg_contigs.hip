@@ -242,7 +242,7 @@ int mg_build_contigs(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edges,
   ctx->contigs.ready = false;
   if ((n_edges && !edges) || (n_list && (!reads || !offs || !ors))) return set_err(ctx, "mg_build_contigs: null argument");
   MG_TRY(hipSetDevice(ctx->device));
-  if (!ctx->n || !ctx->d_words || !ctx->d_len) return set_err(ctx, "mg_build_contigs: no reads on the device");
+  if (!ctx->n || !ctx->d_words.p || !ctx->d_len.p) return set_err(ctx, "mg_build_contigs: no reads on the device");
   // first piece of every edge; list ranges must lie inside the lists
   std::vector<uint64_t> pbase;
   if (edge_bases(ctx, "mg_build_contigs", edges, n_edges, n_list, 2, pbase)) return -1;

@@ -3,12 +3,17 @@
 // exchange; mg_dataset.hip: Dataset ingest on the device; mg_disc.hip: the
 // per-read discovery lists D(A); mg_comp.hip: their components; mg_mates.hip:
 // read lookup and the per-read mate lists; mg_contigs.hip: the strings of edges;
-// mg_places.hip: read placements, insert sizes and edge coverage).  The core
-// fields of mg_ctx belong to mg_kernels.hip; each derived stage keeps its
-// state in one struct (DiscStage .. PlaceStage: ready flag, counts, test
-// options, DevArray buffers, EventPair) that mg_ctx embeds by value; their
-// destructors free them when mg_destroy deletes the context.  What the stage files share beyond the context
-// (call-lifetime scratch, the read view, CSR helpers) is in mg_stage.hpp.
+// mg_places.hip: read placements, insert sizes and edge coverage; mg_paths.hip:
+// mate-pair paths).  The core fields of mg_ctx belong to mg_kernels.hip; each
+// derived stage keeps its state in one struct (DiscStage .. PathStage: ready
+// flag, counts, test options, buffers, EventPair) that mg_ctx embeds by value.
+// The whole context follows one ownership model: every resident device buffer
+// is a DevArray (grown with MG_GROW / MG_ENSURE, freed by its destructor when
+// mg_destroy deletes the context), every call-lifetime buffer a Scratch, and
+// both allocate through ctx_malloc; the plain pointers left in mg_ctx are
+// aliases into those arrays or into the caller's memory and own nothing.
+// What the stage files share beyond this (the read view, CSR helpers) is in
+// mg_stage.hpp.
 #ifndef MG_CTX_HPP_
 #define MG_CTX_HPP_
 #include <hip/hip_runtime.h>
@@ -40,8 +45,8 @@ static_assert(slot_id_word(1) == -1 && slot_id_word(2) == -1 && slot_id_word(3) 
 
 // A device array that lives as long as the context and is freed with it
 // (mg_destroy deletes the context with its device set and its stream idle):
-// pointer and capacity travel together (mg_disc.hip swaps two of them whole).
-// The stage files grow one with MG_GROW (below).
+// pointer and capacity travel together (a layout commit and mg_disc.hip swap
+// two of them whole).  Grown with MG_GROW / MG_ENSURE (below).
 template <typename T>
 struct DevArray {
   T* p = nullptr;
@@ -49,15 +54,33 @@ struct DevArray {
   DevArray() = default;
   DevArray(const DevArray&) = delete;
   DevArray& operator=(const DevArray&) = delete;
-  ~DevArray() {
-    if (p) (void)hipFree(p);
-  }
+  ~DevArray() { release(); }
   // at least `count` elements (contents not kept); `what` names the buffer in the error message
   hipError_t ensure(mg_ctx* ctx, size_t count, const char* what);
   void swap(DevArray& o) {
     std::swap(p, o.p);
     std::swap(cap, o.cap);
   }
+  void release() {
+    if (p) (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+// Device memory for the length of one call, allocated through ctx_malloc under
+// a readable name (option "alloc_cap" and the allocation message apply) and
+// freed on return.  p stays null until alloc(): hipcub's size queries take it so.
+template <typename T>
+struct Scratch {
+  T* p = nullptr;
+  Scratch() = default;
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() {
+    if (p) (void)hipFree(p);
+  }
+  hipError_t alloc(mg_ctx* ctx, size_t count, const char* what);
 };
 
 // The two events a stage times itself with, created on first use, destroyed
@@ -199,9 +222,8 @@ struct mg_ctx {
   uint32_t maxw = 0;
   uint32_t stride = 0;  // words per device slot (slot_words(maxw))
   uint32_t minlen = 0, maxlen = 0;
-  uint64_t* d_words = nullptr;
-  uint16_t* d_len = nullptr;
-  size_t words_cap = 0, len_cap = 0;
+  DevArray<uint64_t> d_words;
+  DevArray<uint16_t> d_len;
   // device layout (option "layout"): slots clustered by each
   // read's canonical global minimizer, so overlapping reads sit near each
   // other; d_id[slot] = reference ID - 1, d_phys[ID - 1] = slot (both nullptr:
@@ -212,38 +234,30 @@ struct mg_ctx {
   // range holds exactly its reference IDs.
   bool layout = true;
   int layout_hash = 0;  // option "layout_hash": the layout's 16-mer hash (0 fmix32, 1 24-bit multiply-adds)
-  uint32_t* d_id = nullptr;    // one of id_store[], or nullptr
-  uint32_t* d_phys = nullptr;  // one of phys_store[], or nullptr
-  uint32_t* id_store[2] = {nullptr, nullptr};  // a re-layout builds the maps in the unused pair
-  uint32_t* phys_store[2] = {nullptr, nullptr};
-  size_t id_cap[2] = {0, 0}, phys_cap[2] = {0, 0};
+  uint32_t* d_id = nullptr;    // alias: one of id_store[], or nullptr
+  uint32_t* d_phys = nullptr;  // alias: one of phys_store[], or nullptr
+  DevArray<uint32_t> id_store[2];  // a re-layout builds the maps in the unused pair
+  DevArray<uint32_t> phys_store[2];
   uint64_t layout_lo = 0, layout_hi = 0;  // the source-read range the current layout groups (0, 0: none)
   // layout scratch, kept between uploads so a re-upload allocates nothing:
   // sort keys / values (double buffers), the sort's temporary storage, and the
   // second slot array the gather writes (the two slot arrays swap)
-  uint64_t* d_lay_k[2] = {nullptr, nullptr};
-  uint32_t* d_lay_v[2] = {nullptr, nullptr};
-  size_t lay_k_cap[2] = {0, 0}, lay_v_cap[2] = {0, 0};
-  void* d_lay_tmp = nullptr;
-  size_t lay_tmp_cap = 0;
-  uint64_t* d_words_alt = nullptr;
-  size_t words_alt_cap = 0;
-  uint16_t* d_len_alt = nullptr;
-  size_t len_alt_cap = 0;
-  uint32_t* d_tmp32 = nullptr;  // ID-order staging of per-read outputs
-  size_t tmp32_cap = 0;
+  DevArray<uint64_t> d_lay_k[2];
+  DevArray<uint32_t> d_lay_v[2];
+  DevArray<uint8_t> d_lay_tmp;
+  DevArray<uint64_t> d_words_alt;
+  DevArray<uint16_t> d_len_alt;
+  DevArray<uint32_t> d_tmp32;  // ID-order staging of per-read outputs
   // index
   uint32_t l = 0, h = 0, m = 0, w = 0;
   uint32_t nb_log2 = 0, nb_log2_opt = 0;
   bool index_ready = false;
-  uint64_t* d_cells = nullptr;  // cells of kCell entries (this rank's bucket range)
-  size_t cells_cap = 0;
+  DevArray<uint64_t> d_cells;  // cells of kCell entries (this rank's bucket range)
   // option "cells_double" (default off): a second table, cleared on the side
   // stream for the next build (cells_alt_clean entries, done at ev[13]).
   // Measured: the clear beside the scan slowed the scan more than the clear
   // costs (C3 scan 2.22 -> 2.72 ms, step 6.91 -> 7.26; profiles/r06s_ab_cells_double.txt)
-  uint64_t* d_cells_alt = nullptr;
-  size_t cells_alt_cap = 0;
+  DevArray<uint64_t> d_cells_alt;
   size_t cells_alt_clean = 0;
   bool cells_double = false;
   // the index holds the o = 1 keys (suffix keys of the forward strand) only
@@ -256,21 +270,19 @@ struct mg_ctx {
   // live discovery index: containment drops o = 1/3 hits, discovery walks the
   // live table, which has them)
   bool index_o3 = true;
-  uint64_t* d_lkcells = nullptr;
-  size_t lkcells_cap = 0;
+  DevArray<uint64_t> d_lkcells;
   bool lookup_ready = false;
   uint64_t cell_lo = 0, cell_n = 0;  // local bucket range [cell_lo, cell_lo + cell_n)
   // containment
-  unsigned long long* d_superkey = nullptr;
-  unsigned long long* superkey = nullptr;  // the containment key array in use (d_superkey or caller-owned)
-  uint32_t* d_super = nullptr;
+  DevArray<unsigned long long> d_superkey;
+  unsigned long long* superkey = nullptr;  // alias: the containment key array in use (d_superkey or caller-owned)
+  DevArray<uint32_t> d_super;
   // contained slots as a bitmap (bit a of word a / 32 = d_super[a] != 0,
   // k_super_finalize): the discovery probe drops contained partners before
   // they take a verification (:548), from a 1/32-size array that stays in cache
-  uint32_t* d_cbits = nullptr;
-  size_t cbits_cap = 0;
+  DevArray<uint32_t> d_cbits;
   // contained reads counted by k_super_finalize (64 counters, one per 64-B line)
-  unsigned int* d_ccnt = nullptr;
+  DevArray<unsigned int> d_ccnt;
   uint64_t n_contained = 0;
   // discovery index (option "live_index", unsharded fused path, mixed lengths):
   // after markContainedReads the discovery probe only needs the keys of
@@ -283,23 +295,21 @@ struct mg_ctx {
   bool live_overlap = true;
   hipStream_t side = nullptr;
   bool live_ready = false;
-  uint64_t* d_lcells = nullptr;
-  size_t lcells_cap = 0;
+  DevArray<uint64_t> d_lcells;
   uint32_t lnb_log2 = 0;
   uint64_t live_cells = 0;  // cells of the discovery index (mg_counters::live_cells)
-  unsigned int* d_any = nullptr;
-  unsigned long long* d_digest = nullptr;  // mg_rows_digest / mg_super_digest accumulators (4 u64)
-  size_t super_cap = 0, superkey_cap = 0;
+  DevArray<unsigned int> d_any;  // k_super_finalize's "some read is contained" word
+  DevArray<unsigned long long> d_digest;  // mg_rows_digest / mg_super_digest accumulators (4 u64)
   bool contained_done = false, super_any = false;
-  // rows
-  uint32_t* d_rows = nullptr;
-  uint64_t rows_cap = 0, rows_cap_opt = 0;
-  unsigned long long* d_seg = nullptr;
+  // rows: d_rows counts rows (its capacity divides into one region per probe
+  // wavefront); the kernels address them as three 32-bit words each (row_words)
+  DevArray<mg_edge> d_rows;
+  uint64_t rows_cap_opt = 0;
+  DevArray<unsigned long long> d_seg;  // rows per region
   uint64_t n_rows = 0;
   std::vector<unsigned long long> seg_host;
-  uint64_t seg_cap_regions = 0;
   bool stats = false;
-  unsigned long long* d_stats = nullptr;
+  DevArray<unsigned long long> d_stats;  // kSegs * 4 + 1 work counters (zero_stats)
   mg_counters counters{};
   // host-side counters of the current step (mg_counters, kept without option "stats"):
   // discovery reruns after a row overflow (settle_rows), rescans after a run-region
@@ -315,14 +325,11 @@ struct mg_ctx {
   int n_cu = 256;              // compute units of the device
   uint64_t nreg = 0;           // row regions of the last discovery launch (one per probe wavefront)
   uint64_t nrun_reg = 0;       // run regions (one per scan wavefront)
-  ulonglong2* d_runs = nullptr;  // run records, one region per wavefront
-  size_t runs_cap = 0;
+  DevArray<ulonglong2> d_runs;  // run records, one region per wavefront
   uint64_t run_cap = 0, run_cap_need = 0, run_cap_opt = 0;  // run_cap_opt: option "run_cap" (tests)
-  unsigned long long* d_run_cnt = nullptr;
-  size_t run_cnt_cap = 0;
+  DevArray<unsigned long long> d_run_cnt;
   std::vector<unsigned long long> run_cnt_host;
-  uint32_t* d_compact = nullptr;
-  size_t compact_cap = 0;
+  DevArray<uint32_t> d_compact;  // mg_copy_rows: the row regions gathered into one array
   // exchange mode (one process per GPU): mg_xchg_begin's scan
   // leaves key records (d_kb / d_ke) and the run regions of this rank's
   // sources; packable = bit mask of what mg_xchg_pack can route now
@@ -336,24 +343,20 @@ struct mg_ctx {
   // caller's marks (all-reduced before mg_xchg_probe(1) folds them in)
   uint64_t scan_runs = 0;  // run records of the last window scan (settle_runs)
   bool xmarks_done = false;
-  uint8_t* xmarks = nullptr;
+  uint8_t* xmarks = nullptr;  // alias: the caller's marks array (mg_xchg_prefix_marks)
   uint64_t xchg_lo = 0, xchg_hi = 0;     // its source reads
-  unsigned long long* d_blk = nullptr;   // routing: per-(block, rank) counts / offsets
-  size_t blk_cap = 0;
+  DevArray<unsigned long long> d_blk;    // routing: per-(block, rank) counts / offsets
   // exchange mode, equal lengths: the register scan counts its runs per
   // destination rank (one row of nranks per run region), so routing the runs
   // skips k_part's count pass (runs_counted: valid for the last scan)
-  unsigned long long* d_rcnt = nullptr;
-  size_t rcnt_cap = 0;
+  DevArray<unsigned long long> d_rcnt;
   // k_xchg_keys' per-(flat region, rank) counts of the key records (keys first):
   // mg_xchg_pack(MG_KEYS) skips k_part's count pass while keys_counted
   // the keys-first receiver scan's run regions hold 8-B metas, d_rdst their owner ranks
-  uint8_t* d_rdst = nullptr;
-  size_t rdst_cap = 0;
+  DevArray<uint8_t> d_rdst;
   bool runs_meta8 = false;
   uint64_t super_zero_n = 0;  // leading d_super entries known to be 0 (skips the equal-length clear)
-  unsigned long long* d_kblk = nullptr;
-  size_t kblk_cap = 0;
+  DevArray<unsigned long long> d_kblk;
   bool keys_counted = false;
   bool runs_counted = false;
   // mg_build_index leaves its timings (index_ms, shared_scan_ms) to be read once
@@ -362,8 +365,7 @@ struct mg_ctx {
   bool index_times_pending = false;
   // exchange-mode discovery probe: rows per (probe wavefront, destination
   // rank), so routing the rows skips k_part's count pass (rows_counted)
-  unsigned long long* d_dcnt = nullptr;
-  size_t dcnt_cap = 0;
+  DevArray<unsigned long long> d_dcnt;
   bool rows_counted = false;
   // option "xchg_route_rows" (default 1): the exchange-mode discovery probe
   // counts its rows per src owner for mg_xchg_pack(MG_ROWS); a host that keeps
@@ -375,13 +377,10 @@ struct mg_ctx {
   uint32_t xchg_region = 512;  // option "xchg_region": records per probe region of the received runs (0: 1,024)
   uint32_t xchg_split_max = 4;  // option "xchg_split_max": mg_xchg_probe_own splits the probe at up to this many ranks
   int packable = 0;                      // 1 << MG_KEYS | 1 << MG_RUNS | 1 << MG_ROWS
-  unsigned long long* d_flat_cnt = nullptr;  // per-region counts of the received runs (probe input)
-  size_t flat_cnt_cap = 0;
-  unsigned long long* d_slot_cnt = nullptr;  // per-region counts of a slot-layout buffer (digest)
-  size_t slot_cnt_cap = 0;
-  uint32_t* d_kb = nullptr;  // key records: bucket / index entry, key o of read a at o * n + a
-  uint64_t* d_ke = nullptr;
-  size_t kb_cap = 0, ke_cap = 0;
+  DevArray<unsigned long long> d_flat_cnt;  // per-region counts of the received runs (probe input)
+  DevArray<unsigned long long> d_slot_cnt;  // per-region counts of a slot-layout buffer (digest)
+  DevArray<uint32_t> d_kb;  // key records: bucket / index entry, key o of read a at o * n + a
+  DevArray<uint64_t> d_ke;
   // timing
   hipEvent_t ev[16] = {};  // [14], [15]: apply_layout
   // unsharded contexts build the index inside the window scan (k_scan<INDEX>);
@@ -394,24 +393,19 @@ struct mg_ctx {
   // prefix containments (k_prefix_contain): each read's o = 0 key (bucket,
   // fingerprint, q) written by k_scan<INDEX> for mixed-length sets; when ready
   // the containment probe skips suffix-key hits (containment)
-  uint64_t* d_key0 = nullptr;
-  size_t key0_cap = 0;
+  DevArray<uint64_t> d_key0;
   // offset-0 containments through the containment probe (option prefix_probe,
   // default): the fused scan writes each read's window-0 run (its o = 0 key's
   // minimizer, window range [0, 0]) here, one 16-B record per slot, and the
   // probe takes them first in fixed regions of d_p0cnt records
   bool prefix_probe = true;
-  ulonglong2* d_p0runs = nullptr;
-  size_t p0runs_cap = 0;
-  unsigned long long* d_p0cnt = nullptr;
-  size_t p0cnt_cap = 0;
+  DevArray<ulonglong2> d_p0runs;
+  DevArray<unsigned long long> d_p0cnt;
   // exchange mode: the received runs ordered by local bucket (sort_xruns), the
   // input of both probes; xruns_ready until the next mg_xchg_begin
-  uint32_t* d_xk[2] = {nullptr, nullptr};
-  ulonglong2* d_xv[2] = {nullptr, nullptr};
-  size_t xk_cap[2] = {0, 0}, xv_cap[2] = {0, 0};
-  void* d_xsort_tmp = nullptr;
-  size_t xsort_tmp_cap = 0;
+  DevArray<uint32_t> d_xk[2];
+  DevArray<ulonglong2> d_xv[2];
+  DevArray<uint8_t> d_xsort_tmp;  // the sort / scan / select scratch of the exchange build
   int xv_sel = 0;
   uint64_t xruns_n = 0;
   bool own_probed = false;
@@ -422,37 +416,35 @@ struct mg_ctx {
   bool xchg_keys_first = true;
   bool keys_first = false;  // the current exchange build is a keys-first one
   bool rk_on = false;
-  const uint64_t* rk_keys = nullptr;
+  const uint64_t* rk_keys = nullptr;  // aliases: the caller's receive buffer and its counts, during that launch
   const unsigned long long* rk_cnt = nullptr;
   uint64_t rk_slot = 0, rk_total = 0;
   int xruns_part = 0;       // the probe regions prepared: 0 all, 1 own stream, 2 the peers' (split probe)
   uint64_t xruns_K = 0;     // probe regions per peer slot and round  // mg_xchg_probe_own probed this rank's own stream; mg_xchg_probe(0) appends the peers
   // the received runs expanded to 16-B probe records (k_xruns_expand), slot layout
-  ulonglong2* d_xexp = nullptr;
-  size_t xexp_cap = 0;
+  DevArray<ulonglong2> d_xexp;
   bool xruns_ready = false;
-  ulonglong2* xruns_base = nullptr;  // the probes' run regions: d_xv (sorted), the receive buffer, or (one rank) d_runs
-  unsigned long long* xruns_cnt = nullptr;  // their per-region counts
+  ulonglong2* xruns_base = nullptr;  // alias: the probes' run regions: d_xv (sorted), d_xexp, or (one rank) d_runs
+  unsigned long long* xruns_cnt = nullptr;  // alias: their per-region counts (d_flat_cnt, or d_run_cnt)
   uint64_t xruns_reg = 0, xruns_nreg = 0;
   // exchange mode: the key records this rank received, dense and sorted by
   // home cell (mg_xchg_insert_keys: key = local home cell, ent = index
   // entry); they build the cells, the o = 0 ones drive the prefix containments
   // (k_prefix_contain_keys, xchg_prefix) and the live ones the discovery index
-  uint32_t* d_xkk[2] = {nullptr, nullptr};
-  uint64_t* d_xke[2] = {nullptr, nullptr};
-  size_t xkk_cap[2] = {0, 0}, xke_cap[2] = {0, 0};
+  DevArray<uint32_t> d_xkk[2];
+  DevArray<uint64_t> d_xke[2];
   uint64_t xkeys_n = 0;
   uint32_t xkey_cls = 0;       // 1: key = home cell << 1 | (o == 3) (the full table leaves out o = 3)
   uint32_t xkey_fs = 0;        // low fingerprint bits below the cell / class bits (chain_par)
   bool xkey_par = false;       // the received records' cells are built by the parallel placement
-  uint32_t* xkey_k = nullptr;  // the sorted records (one of d_xkk[] / d_kb) and the other buffer pair
+  // aliases: the sorted records (one of d_xkk[] / d_kb, d_xke[] / d_ke) and the other buffer pair
+  uint32_t* xkey_k = nullptr;
   uint64_t* xkey_e = nullptr;
   uint32_t* xkey_k_alt = nullptr;
   uint64_t* xkey_e_alt = nullptr;
   // the live records' in-order compaction (build_live_index_xchg)
-  uint8_t* d_xflag = nullptr;
-  size_t xflag_cap = 0;
-  unsigned long long* d_nlive = nullptr;
+  DevArray<uint8_t> d_xflag;
+  DevArray<unsigned long long> d_nlive;  // their count (one word)
   // the exchange mode's discovery index coarsens the rank's cells (cell =
   // local home cell >> live_shift) instead of rebuilding entries
   bool live_coarse = false;
@@ -467,9 +459,8 @@ struct mg_ctx {
   bool chain_par = true;
   bool check_cells = false;  // diagnostics (option "check_cells"): verify each sorted cell build
   int xchg_fs = -1;  // diagnostics (option "xchg_fs"): fingerprint bits in the exchange sort key (-1: fp_sort_bits)
-  uint32_t* d_rhead = nullptr;
-  uint32_t* d_rstart = nullptr;
-  size_t rhead_cap = 0, rstart_cap = 0;
+  DevArray<uint32_t> d_rhead;
+  DevArray<uint32_t> d_rstart;
   bool xchg_prefix = false;
   bool key0_ready = false;
   bool prefix_contain = true;  // option "prefix_contain"
@@ -480,8 +471,7 @@ struct mg_ctx {
   float shared_scan_ms = 0.f;  // k_scan<INDEX> kernel time of the last mg_build_index
   mg_timings t{};
   // Dataset ingest on the device (mg_ingest_*): frequency of each unique read
-  uint32_t* d_freq = nullptr;
-  size_t freq_cap = 0;
+  DevArray<uint32_t> d_freq;
   uint64_t n_good = 0;  // reads that passed testRead (Dataset::getNumberOfReads)
   // option "alloc_cap" (tests): a device allocation above this many bytes fails
   // as out of memory (0 = no cap), so the error path is exercised on purpose
@@ -529,36 +519,44 @@ inline hipError_t ctx_malloc(mg_ctx* ctx, void** p, size_t bytes, const char* wh
   return e;
 }
 
-// grow *p to at least `count` elements (contents not kept)
-template <typename T>
-inline hipError_t ensure(mg_ctx* ctx, T** p, size_t* cap, size_t count, const char* what) {
-  if (*cap >= count && *p) return hipSuccess;
-  if (*p) {
-    hipError_t e = hipFree(*p);
-    if (e != hipSuccess) return e;
-    *p = nullptr;
-    *cap = 0;
-  }
-  const size_t c = std::max<size_t>(count, 1);
-  hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(p), c * sizeof(T), what);
-  if (e == hipSuccess) *cap = c;
-  return e;
-}
-// ensure() of a context field; returns -1 from the caller with ctx->err set
-#define MG_ENSURE(field, capf, count)                                                            \
-  do {                                                                                          \
-    if (ensure(ctx, &ctx->field, &ctx->capf, (count), #field) != hipSuccess) return -1;         \
-  } while (0)
+// (a failure leaves its cause in ctx->err: ctx_malloc's message, or the failed free of the old buffer)
 template <typename T>
 inline hipError_t DevArray<T>::ensure(mg_ctx* ctx, size_t count, const char* what) {
-  return ::ensure(ctx, &p, &cap, count, what);
+  if (cap >= count && p) return hipSuccess;
+  if (p) {
+    const hipError_t e = hipFree(p);
+    if (e != hipSuccess) {
+      ctx->err = std::string("freeing ") + what + " to grow it failed: " + hipGetErrorString(e);
+      return e;
+    }
+    p = nullptr;
+    cap = 0;
+  }
+  const size_t c = std::max<size_t>(count, 1);
+  const hipError_t e = ctx_malloc(ctx, reinterpret_cast<void**>(&p), c * sizeof(T), what);
+  if (e == hipSuccess) cap = c;
+  return e;
 }
-// DevArray::ensure() of a stage's array under the name its messages carry (the
-// d_* names callers know); returns -1 from the caller with ctx->err set
+template <typename T>
+inline hipError_t Scratch<T>::alloc(mg_ctx* ctx, size_t count, const char* what) {
+  return ctx_malloc(ctx, reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), what);
+}
+// DevArray::ensure() under the name the buffer's messages carry (the d_* names
+// callers know); returns -1 from the caller with ctx->err set
 #define MG_GROW(arr, count, what)                                         \
   do {                                                                    \
     if ((arr).ensure(ctx, (count), (what)) != hipSuccess) return -1;      \
   } while (0)
+// MG_GROW of a core field of the context under the field's own name
+#define MG_ENSURE(field, count) MG_GROW(ctx->field, (count), #field)
+// Scratch::alloc(); returns -1 from the caller with ctx->err set
+#define MG_SCRATCH(buf, count, what)                                      \
+  do {                                                                    \
+    if ((buf).alloc(ctx, (count), (what)) != hipSuccess) return -1;       \
+  } while (0)
+// the context's rows as the kernels address them: three 32-bit words per row
+static_assert(sizeof(mg_edge) == 3 * sizeof(uint32_t), "a row is three 32-bit words");
+inline uint32_t* row_words(const mg_ctx* ctx) { return reinterpret_cast<uint32_t*>(ctx->d_rows.p); }
 // a launch wrapper that failed: keep the cause a callee left in ctx->err
 inline int launch_fail(mg_ctx* ctx, const std::string& what) {
   ctx->err = ctx->err.empty() ? what : what + ": " + ctx->err;

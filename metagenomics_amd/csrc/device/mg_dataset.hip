@@ -342,15 +342,15 @@ struct Ingest {
     ctx->maxw = ngood ? maxw : supported_maxw(1);
     ctx->stride = slot_stride(ctx->maxw);
     const size_t nw = (size_t)(nu + 2) * ctx->stride + 2;  // zero pad for over-reads
-    MG_ENSURE(d_words, words_cap, nw);
-    MG_ENSURE(d_len, len_cap, nu + 1);
-    MG_ENSURE(d_freq, freq_cap, nu + 1);
-    MG_TRY(hipMemsetAsync(ctx->d_words, 0, nw * sizeof(uint64_t), st));
+    MG_ENSURE(d_words, nw);
+    MG_ENSURE(d_len, nu + 1);
+    MG_ENSURE(d_freq, nu + 1);
+    MG_TRY(hipMemsetAsync(ctx->d_words.p, 0, nw * sizeof(uint64_t), st));
     MG_SCRATCH(first, nu, "ingest run firsts");
     if (ngood) {
       hipLaunchKernelGGL((k_dedup_write<W>), dim3(blocks_for(ngood)), dim3(kThreads), 0, st, canon.p, len.p, cur, start.p,
-                         uid.p, ngood, ctx->maxw, ctx->stride, ctx->d_words, ctx->d_len, first.p, CW);
-      hipLaunchKernelGGL(k_dedup_freq, dim3(blocks_for(nu)), dim3(kThreads), 0, st, first.p, nu, ngood, ctx->d_freq);
+                         uid.p, ngood, ctx->maxw, ctx->stride, ctx->d_words.p, ctx->d_len.p, first.p, CW);
+      hipLaunchKernelGGL(k_dedup_freq, dim3(blocks_for(nu)), dim3(kThreads), 0, st, first.p, nu, ngood, ctx->d_freq.p);
       MG_TRY(hipGetLastError());
     }
     MG_TRY(hipStreamSynchronize(st));
@@ -505,8 +505,8 @@ int mg_dataset_counts(const mg_ctx* ctx, uint64_t* n_good, uint64_t* n_unique) {
 int mg_download_frequency(mg_ctx* ctx, uint32_t* freq) {
   if (!ctx || !freq) return -1;
   MG_TRY(hipSetDevice(ctx->device));
-  if (!ctx->d_freq) return set_err(ctx, "no device-ingested Dataset");
-  if (ctx->n) MG_TRY(hipMemcpy(freq, ctx->d_freq, ctx->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  if (!ctx->d_freq.p) return set_err(ctx, "no device-ingested Dataset");
+  if (ctx->n) MG_TRY(hipMemcpy(freq, ctx->d_freq.p, ctx->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
   return 0;
 }
 

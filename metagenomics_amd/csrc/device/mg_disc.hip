@@ -345,18 +345,18 @@ int group_rows(mg_ctx* ctx) {
   MG_GROW(ds.tmp, tb, "d_disc_tmp");
   tb = ds.tmp.cap;
 
-  const uint64_t reg_cap = ctx->rows_cap / ctx->nreg;
+  const uint64_t reg_cap = ctx->d_rows.cap / ctx->nreg;
   const uint32_t walk = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(ctx->nreg, (uint64_t)ctx->n_cu * 32));
   MG_TRY(ctl_fill(ctx->stream, ds.ctl.p, kDiscCtl, 0));
   MG_TRY(hipMemsetAsync(ds.cnt.p, 0, entries * sizeof(uint32_t), ctx->stream));
-  hipLaunchKernelGGL(k_disc_count, dim3(walk), dim3(kThreads), 0, ctx->stream, ctx->d_rows, reg_cap, ctx->d_seg,
+  hipLaunchKernelGGL(k_disc_count, dim3(walk), dim3(kThreads), 0, ctx->stream, row_words(ctx), reg_cap, ctx->d_seg.p,
                      ctx->nreg, (uint32_t)N, ds.cnt.p, ds.ctl.p);
   MG_TRY(hipGetLastError());
   MG_TRY(rocprim::exclusive_scan(ds.tmp.p, tb, ds.cnt.p, ds.start.p, (uint64_t)0,
                                  (size_t)entries, rocprim::plus<uint64_t>(), ctx->stream));
   MG_TRY(hipMemsetAsync(ds.cnt.p, 0, entries * sizeof(uint32_t), ctx->stream));
-  hipLaunchKernelGGL(k_disc_scatter, dim3(walk), dim3(kThreads), 0, ctx->stream, ctx->d_rows, reg_cap, ctx->d_seg,
-                     ctx->nreg, (uint32_t)N, h, ctx->d_len, ctx->d_phys, ds.start.p, ds.cnt.p,
+  hipLaunchKernelGGL(k_disc_scatter, dim3(walk), dim3(kThreads), 0, ctx->stream, row_words(ctx), reg_cap, ctx->d_seg.p,
+                     ctx->nreg, (uint32_t)N, h, ctx->d_len.p, ctx->d_phys, ds.start.p, ds.cnt.p,
                      ds.recs.p, ds.ctl.p);
   MG_TRY(hipGetLastError());
   hipLaunchKernelGGL(k_disc_classify, dim3(blocks_for(N)), dim3(kThreads), 0, ctx->stream, ds.start.p,
@@ -364,11 +364,11 @@ int group_rows(mg_ctx* ctx) {
   MG_TRY(hipGetLastError());
   const uint64_t waves = (N + kWaveReads - 1) / kWaveReads;
   hipLaunchKernelGGL(k_disc_wave, dim3(blocks_for(waves * kWave)), dim3(kThreads), 0, ctx->stream, ds.recs.p,
-                     ds.start.p, (uint32_t)N, h, ctx->d_len, ctx->d_phys, ds.ctl.p);
+                     ds.start.p, (uint32_t)N, h, ctx->d_len.p, ctx->d_phys, ds.ctl.p);
   MG_TRY(hipGetLastError());
   const uint32_t per_read_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(list_n, (uint64_t)ctx->n_cu * 8));
   hipLaunchKernelGGL(k_disc_block, dim3(per_read_grid), dim3(kThreads), 0, ctx->stream, ds.recs.p,
-                     ds.start.p, ds.list.p, list_n, h, ctx->d_len, ctx->d_phys, ds.ctl.p);
+                     ds.start.p, ds.list.p, list_n, h, ctx->d_len.p, ctx->d_phys, ds.ctl.p);
   MG_TRY(hipGetLastError());
   // the class counts (and, so far, the error bits) after everything above is queued
   unsigned long long ctl[kDiscCtl];
@@ -391,7 +391,7 @@ int group_rows(mg_ctx* ctx) {
                                               (unsigned int)big_total, (unsigned int)n_big, ds.boff.p,
                                               ds.boff.p + 1, 0u, 50u, ctx->stream));
     hipLaunchKernelGGL(k_disc_big_records, dim3(g), dim3(kThreads), 0, ctx->stream, ds.recs.p, ds.start.p,
-                       ds.list.p, list_n, ds.boff.p, n_big, ds.big[1].p, h, ctx->d_len,
+                       ds.list.p, list_n, ds.boff.p, n_big, ds.big[1].p, h, ctx->d_len.p,
                        ctx->d_phys, ds.ctl.p);
     MG_TRY(hipGetLastError());
     MG_TRY(ctl_read(ctx->stream, ds.ctl.p, kDiscCtl, ctl));

@@ -481,8 +481,8 @@ struct LaunchPrefixContainKeys {
     if (!n) return 0;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(
         1, std::min<uint64_t>((n + kBlock - 1) / kBlock, (uint64_t)ctx->n_cu * 16));
-    hipLaunchKernelGGL(k_prefix_contain_keys<W>, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->d_words, ctx->d_len,
-                       ctx->xkey_k, ctx->xkey_e, n, ctx->xkey_cls + ctx->xkey_fs, ctx->d_cells, ctx->cell_n,
+    hipLaunchKernelGGL(k_prefix_contain_keys<W>, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->d_words.p, ctx->d_len.p,
+                       ctx->xkey_k, ctx->xkey_e, n, ctx->xkey_cls + ctx->xkey_fs, ctx->d_cells.p, ctx->cell_n,
                        ctx->superkey, ctx->d_id);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
@@ -493,7 +493,7 @@ struct LaunchPrefixContain {
   static int run(mg_ctx* ctx) {
     if (!ctx->n) return 0;
     hipLaunchKernelGGL(k_prefix_contain<W>, dim3((uint32_t)((ctx->n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       ctx->stream, ctx->d_words, ctx->d_len, ctx->d_key0, ctx->d_cells, ctx->cell_n, ctx->nb_log2,
+                       ctx->stream, ctx->d_words.p, ctx->d_len.p, ctx->d_key0.p, ctx->d_cells.p, ctx->cell_n, ctx->nb_log2,
                        ctx->n, ctx->superkey, ctx->d_id);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
@@ -607,7 +607,7 @@ struct LaunchXkeysDense {
   static int run(mg_ctx* ctx, const uint64_t* recv, uint64_t slot, uint32_t rounds, const unsigned long long* counts,
                  uint32_t* key, uint64_t* ent) {
     hipLaunchKernelGGL(k_xkeys_dense<W>, slot_grid(slot, rounds, ctx->nranks), dim3(kBlock), 0, ctx->stream, recv, slot,
-                       ctx->nranks, (uint64_t)rounds * slot, counts, ctx->d_words, ctx->d_len, (int)ctx->h,
+                       ctx->nranks, (uint64_t)rounds * slot, counts, ctx->d_words.p, ctx->d_len.p, (int)ctx->h,
                        (int)ctx->m, (int)ctx->w, ctx->nb_log2, ctx->cell_lo, ctx->xkey_cls, ctx->xkey_fs, key, ent);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
@@ -618,7 +618,7 @@ struct LaunchXrunsExpand {
   static int run(mg_ctx* ctx, const uint64_t* recv, uint64_t slot, uint32_t rounds, const unsigned long long* counts,
                  ulonglong2* out, int part) {
     hipLaunchKernelGGL(k_xruns_expand<W>, slot_grid(slot, rounds, ctx->nranks), dim3(kBlock), 0, ctx->stream, recv,
-                       slot, ctx->nranks, counts, ctx->d_words, (int)ctx->m, out, part, ctx->rank);
+                       slot, ctx->nranks, counts, ctx->d_words.p, (int)ctx->m, out, part, ctx->rank);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
 };
@@ -3222,7 +3222,7 @@ struct LaunchLayout {
   static int run(mg_ctx* ctx, uint64_t lo, uint64_t hi, int grouped, int pb, uint64_t* key, uint32_t* val) {
     const uint64_t n = ctx->n;
     hipLaunchKernelGGL((k_layout_keys<W>), dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       ctx->d_words, ctx->d_len, n, ctx->d_id, lo, hi, grouped, pb, ctx->layout_hash, key, val);
+                       ctx->d_words.p, ctx->d_len.p, n, ctx->d_id, lo, hi, grouped, pb, ctx->layout_hash, key, val);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
 };
@@ -3232,7 +3232,7 @@ struct LaunchLayoutGather {
     constexpr int S = slot_words(W);
     const uint64_t t = ctx->n * (uint64_t)(S >= 2 ? S / 2 : 1);
     hipLaunchKernelGGL((k_layout_gather<W>), dim3((uint32_t)((t + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       ctx->d_words, ctx->d_len, ctx->d_id, order, ctx->n, dst_words, dst_len, id);
+                       ctx->d_words.p, ctx->d_len.p, ctx->d_id, order, ctx->n, dst_words, dst_len, id);
     return hipGetLastError() == hipSuccess ? 0 : -1;
   }
 };
@@ -3270,8 +3270,8 @@ void allow_lds(K kernel, size_t bytes) {
 
 IndexParams index_params(mg_ctx* ctx) {
   IndexParams p{};
-  p.words = ctx->d_words;
-  p.len = ctx->d_len;
+  p.words = ctx->d_words.p;
+  p.len = ctx->d_len.p;
   p.n = ctx->n;
   p.h = (int)ctx->h;
   p.m = (int)ctx->m;
@@ -3281,7 +3281,7 @@ IndexParams index_params(mg_ctx* ctx) {
   p.nranks = ctx->nranks;
   p.cell_lo = ctx->cell_lo;
   p.cell_n = ctx->cell_n;
-  p.cells = ctx->d_cells;
+  p.cells = ctx->d_cells.p;
   p.id = ctx->d_id;
   p.stride = ctx->stride;
   return p;
@@ -3629,28 +3629,15 @@ struct LaunchScan {
     const uint64_t groups_per_region = ((ngroups + G - 1) / G + nw - 1) / nw;  // windows per wave
     uint64_t run_cap = std::max<uint64_t>(
         ctx->run_cap_need, ctx->run_cap_opt ? ctx->run_cap_opt : groups_per_region * kWave * per_read);
-    if (run_cap * nreg > ctx->runs_cap) {
-      if (ctx->d_runs) (void)hipFree(ctx->d_runs);
-      ctx->d_runs = nullptr;
-      ctx->runs_cap = 0;
-      if (ctx_malloc(ctx, (void**)&ctx->d_runs, run_cap * nreg * sizeof(ulonglong2), "d_runs (run regions)")) return -1;
-      ctx->runs_cap = run_cap * nreg;
-    }
-    if (!ctx->run_cap_opt) run_cap = ctx->runs_cap / std::max<uint64_t>(1, nreg);
+    MG_GROW(ctx->d_runs, run_cap * nreg, "d_runs (run regions)");
+    if (!ctx->run_cap_opt) run_cap = ctx->d_runs.cap / std::max<uint64_t>(1, nreg);
     ctx->run_cap = run_cap;
-    if (ctx->run_cnt_cap < nreg) {
-      if (ctx->d_run_cnt) (void)hipFree(ctx->d_run_cnt);
-      ctx->d_run_cnt = nullptr;
-      ctx->run_cnt_cap = 0;
-      if (ctx_malloc(ctx, (void**)&ctx->d_run_cnt, std::max<uint64_t>(1, nreg) * sizeof(unsigned long long), "d_run_cnt"))
-        return -1;
-      ctx->run_cnt_cap = nreg;
-    }
+    MG_ENSURE(d_run_cnt, nreg);
     ctx->runs_live = false;
     ScanParams sp{};
-    sp.words = ctx->d_words;
-    sp.len = ctx->d_len;
-    sp.super = (!no_super && !contain && ctx->contained_done && ctx->super_any) ? ctx->d_super : nullptr;
+    sp.words = ctx->d_words.p;
+    sp.len = ctx->d_len.p;
+    sp.super = (!no_super && !contain && ctx->contained_done && ctx->super_any) ? ctx->d_super.p : nullptr;
     sp.a_lo = a_lo;
     sp.a_hi = a_hi;
     sp.h = (int)ctx->h;
@@ -3659,18 +3646,18 @@ struct LaunchScan {
     sp.nb_log2 = ctx->nb_log2;
     sp.rank = filter ? ctx->rank : 0;
     sp.nranks = filter ? ctx->nranks : 1;
-    sp.runs = ctx->d_runs;
-    sp.run_cnt = ctx->d_run_cnt;
+    sp.runs = ctx->d_runs.p;
+    sp.run_cnt = ctx->d_run_cnt.p;
     sp.run_cap = run_cap;
     const size_t lds = scan_lds(ctx, index);
-    sp.cells = ctx->d_cells;
+    sp.cells = ctx->d_cells.p;
     sp.cell_n = ctx->cell_n;
     sp.cell_lo = ctx->cell_lo;  // (0 unless the cells are a bucket-range shard)
     if (index && ctx->key0_ready) {  // mg_build_index allocated it (mixed lengths)
       if (ctx->prefix_probe)
-        sp.p0runs = ctx->d_p0runs;
+        sp.p0runs = ctx->d_p0runs.p;
       else
-        sp.key0 = ctx->d_key0;
+        sp.key0 = ctx->d_key0.p;
     }
     sp.skip_o1 = (index && !ctx->index_o1) ? 1 : 0;
     sp.skip_o3 = (index && !ctx->index_o3 && !ctx->xchg) ? 1 : 0;
@@ -3681,14 +3668,14 @@ struct LaunchScan {
     // the exchange scan counts its runs per destination rank as it stores them
     // (the register scan per region, k_scan<KEYREC> per region and group: G P <= 64)
     if ((index || recv) && ctx->xchg && ctx->nranks > 1 && G * ctx->nranks <= (uint64_t)kWave) {
-      MG_ENSURE(d_rcnt, rcnt_cap, nreg * ctx->nranks);
-      sp.dst_cnt = ctx->d_rcnt;
+      MG_ENSURE(d_rcnt, nreg * ctx->nranks);
+      sp.dst_cnt = ctx->d_rcnt.p;
       sp.dst_ranks = ctx->nranks;
       ctx->runs_counted = true;
     }
     if (index && ctx->xchg) {  // key records (bucket, entry), o-major: they travel to the bucket owner
-      sp.key_bk = ctx->d_kb;
-      sp.key_ent = ctx->d_ke;
+      sp.key_bk = ctx->d_kb.p;
+      sp.key_ent = ctx->d_ke.p;
       sp.key_n = a_hi - a_lo;  // the rank's sources only
       sp.key_lo = a_lo;
     }
@@ -3706,8 +3693,8 @@ struct LaunchScan {
       }
     } else {
       if (recv) {  // exchange mode, keys first: the runs + the received keys' CAS inserts
-        MG_ENSURE(d_rdst, rdst_cap, run_cap * nreg);
-        sp.run_dst = ctx->d_rdst;
+        MG_ENSURE(d_rdst, run_cap * nreg);
+        sp.run_dst = ctx->d_rdst.p;
         ctx->runs_meta8 = true;
         sp.recv_keys = ctx->rk_keys;
         sp.recv_cnt = ctx->rk_cnt;
@@ -3750,8 +3737,8 @@ struct LaunchProbe {
       return set_err(ctx, "templated probe: reads longer than 1,024 bp must take the long-read kernels");
     ctx->nreg = (uint64_t)grid * kWavesPerBlock;  // probe wavefronts = row regions
     ProbeParams pp{};
-    pp.words = ctx->d_words;
-    pp.len = ctx->d_len;
+    pp.words = ctx->d_words.p;
+    pp.len = ctx->d_len.p;
     pp.h = (int)ctx->h;
     pp.m = (int)ctx->m;
     pp.nb_log2 = ctx->nb_log2;
@@ -3759,20 +3746,20 @@ struct LaunchProbe {
     pp.nranks = ctx->nranks;
     pp.cell_lo = ctx->cell_lo;
     pp.cell_n = ctx->cell_n;
-    pp.cells = ctx->d_cells;
+    pp.cells = ctx->d_cells.p;
     if (!contain && ctx->live_ready && ctx->live_coarse) {  // exchange mode (build_live_index_xchg)
       pp.cell_shift = ctx->live_shift;
       pp.cell_n = ctx->live_cells;
-      pp.cells = ctx->d_lcells;
+      pp.cells = ctx->d_lcells.p;
     } else if (!contain && ctx->live_ready) {  // the discovery index of uncontained reads (build_live_index)
       pp.nb_log2 = ctx->lnb_log2;
       pp.cell_lo = 0;
       pp.cell_n = 1ull << ctx->lnb_log2;
-      pp.cells = ctx->d_lcells;
+      pp.cells = ctx->d_lcells.p;
     }
     // contained partners are dropped at listing (:548), except from the live
     // index, which holds the uncontained reads' keys only
-    pp.cbits = (!contain && ctx->contained_done && ctx->super_any && !ctx->live_ready) ? ctx->d_cbits : nullptr;
+    pp.cbits = (!contain && ctx->contained_done && ctx->super_any && !ctx->live_ready) ? ctx->d_cbits.p : nullptr;
     pp.superkey = ctx->superkey;
     pp.runs = runs;
     pp.run_cnt = run_cnt;
@@ -3781,11 +3768,11 @@ struct LaunchProbe {
     pp.src_super = src_super;
     pp.src_lo = src_lo;
     pp.src_hi = src_hi;
-    pp.rows = ctx->d_rows;
-    pp.reg_cnt = ctx->d_seg;
-    pp.reg_cap = contain ? 0 : ctx->rows_cap / ctx->nreg;
+    pp.rows = row_words(ctx);
+    pp.reg_cnt = ctx->d_seg.p;
+    pp.reg_cap = contain ? 0 : ctx->d_rows.cap / ctx->nreg;
     pp.uniform_len = ctx->minlen == ctx->maxlen ? (int)ctx->maxlen : 0;
-    pp.stats = ctx->stats ? ctx->d_stats : nullptr;
+    pp.stats = ctx->stats ? ctx->d_stats.p : nullptr;
     pp.phase_limit = contain ? ctx->contain_phase_limit : ctx->phase_limit;
     pp.halving_low = ctx->halving_low ? 1 : 0;
     pp.halving_id = (ctx->read_lo || ctx->read_hi) ? ctx->d_id : nullptr;
@@ -3838,8 +3825,8 @@ struct LaunchProbe {
     if (!contain) ctx->rows_counted = false;
     if (!contain) ctx->probe_vsplit = pp.vsplit;
     if (dcnt) {  // the rows' routing takes these counts (mg_xchg_pack, MG_ROWS)
-      MG_ENSURE(d_dcnt, dcnt_cap, ctx->nreg * ctx->nranks);
-      pp.dst_cnt = ctx->d_dcnt;
+      MG_ENSURE(d_dcnt, ctx->nreg * ctx->nranks);
+      pp.dst_cnt = ctx->d_dcnt.p;
       pp.dst_ranks = ctx->nranks;
       pp.n_ids = ctx->n;
       pp.inv_n_ids = 1.0 / (double)ctx->n;
@@ -3871,7 +3858,7 @@ struct LaunchDiscover {
     if (a_hi <= a_lo) return 0;
     const DiscGeom g = disc_geom<W>(ctx, contain, a_hi - a_lo);
     if (LaunchScan<W>::run(ctx, contain, a_lo, a_hi, g.sgrid, !contain)) return -1;
-    return LaunchProbe<W>::run(ctx, contain, ctx->d_runs, ctx->d_run_cnt, ctx->run_cap, ctx->nrun_reg, g.grid);
+    return LaunchProbe<W>::run(ctx, contain, ctx->d_runs.p, ctx->d_run_cnt.p, ctx->run_cap, ctx->nrun_reg, g.grid);
   }
 };
 
@@ -3891,11 +3878,11 @@ struct LaunchPrefixProbe {
     if (!ctx->n) return 0;
     constexpr uint64_t kR = 512;  // records per fixed region (consecutive slots)
     const uint64_t nreg = (ctx->n + kR - 1) / kR;
-    MG_ENSURE(d_p0cnt, p0cnt_cap, nreg);
+    MG_ENSURE(d_p0cnt, nreg);
     hipLaunchKernelGGL(k_fixed_regions, dim3((uint32_t)((nreg + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       ctx->d_p0cnt, ctx->n, kR, nreg);
+                       ctx->d_p0cnt.p, ctx->n, kR, nreg);
     const DiscGeom g = disc_geom<W>(ctx, true, ctx->n);
-    return LaunchProbe<W>::run(ctx, true, ctx->d_p0runs, ctx->d_p0cnt, kR, nreg, g.grid);
+    return LaunchProbe<W>::run(ctx, true, ctx->d_p0runs.p, ctx->d_p0cnt.p, kR, nreg, g.grid);
   }
 };
 
@@ -3924,18 +3911,18 @@ struct LaunchPrefixProbeKeys {
   static int run(mg_ctx* ctx) {
     const uint64_t n = ctx->xkeys_n;
     if (!n) return 0;
-    MG_ENSURE(d_p0runs, p0runs_cap, n);
+    MG_ENSURE(d_p0runs, n);
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>((n + kBlock - 1) / kBlock,
                                                                            (uint64_t)ctx->n_cu * 16));
     hipLaunchKernelGGL(k_p0_from_keys, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->xkey_k, ctx->xkey_e, n,
-                       ctx->xkey_cls + ctx->xkey_fs, ctx->cell_lo, ctx->nb_log2, ctx->d_p0runs);
+                       ctx->xkey_cls + ctx->xkey_fs, ctx->cell_lo, ctx->nb_log2, ctx->d_p0runs.p);
     constexpr uint64_t kR = 512;
     const uint64_t nreg = (n + kR - 1) / kR;
-    MG_ENSURE(d_p0cnt, p0cnt_cap, nreg);
+    MG_ENSURE(d_p0cnt, nreg);
     hipLaunchKernelGGL(k_fixed_regions, dim3((uint32_t)((nreg + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       ctx->d_p0cnt, n, kR, nreg);
+                       ctx->d_p0cnt.p, n, kR, nreg);
     const DiscGeom g = disc_geom<W>(ctx, true, std::max<uint64_t>(1, n / 3));
-    return LaunchProbe<W>::run(ctx, true, ctx->d_p0runs, ctx->d_p0cnt, kR, nreg, g.grid);
+    return LaunchProbe<W>::run(ctx, true, ctx->d_p0runs.p, ctx->d_p0cnt.p, kR, nreg, g.grid);
   }
 };
 
@@ -3962,7 +3949,7 @@ int prefix_contain_pass(mg_ctx* ctx) {
 // getListOfReads reads all four keys: the lookup table when the index left out o = 1
 IndexParams lookup_params(mg_ctx* ctx) {
   IndexParams p = index_params(ctx);
-  if ((!ctx->index_o1 || !ctx->index_o3) && !long_mode(ctx)) p.cells = ctx->d_lkcells;
+  if ((!ctx->index_o1 || !ctx->index_o3) && !long_mode(ctx)) p.cells = ctx->d_lkcells.p;
   return p;
 }
 
@@ -3997,18 +3984,18 @@ int launch_lookup(mg_ctx* ctx, const uint64_t* dq, int qwords, unsigned long lon
 // superkeys) or discovery (rows; regions resized and rerun on overflow)
 int long_probe(mg_ctx* ctx, bool contain, uint64_t a_lo, uint64_t a_hi) {
   LongParams p{};
-  p.words = ctx->d_words;
-  p.len = ctx->d_len;
+  p.words = ctx->d_words.p;
+  p.len = ctx->d_len.p;
   p.stride = ctx->stride;
   p.h = (int)ctx->h;
   p.m = (int)ctx->m;
   p.w = (int)ctx->w;
   p.nb_log2 = ctx->nb_log2;
   p.cell_n = ctx->cell_n;
-  p.cells = ctx->d_cells;
+  p.cells = ctx->d_cells.p;
   p.a_lo = a_lo;
   p.a_hi = a_hi;
-  p.super = (!contain && ctx->contained_done && ctx->super_any) ? ctx->d_super : nullptr;
+  p.super = (!contain && ctx->contained_done && ctx->super_any) ? ctx->d_super.p : nullptr;
   p.superkey = ctx->superkey;
   p.halving_low = ctx->halving_low ? 1 : 0;
   const uint64_t nsrc = a_hi > a_lo ? a_hi - a_lo : 0;
@@ -4022,9 +4009,9 @@ int long_probe(mg_ctx* ctx, bool contain, uint64_t a_lo, uint64_t a_hi) {
   // (the long-read kernels count no work units: option "stats" reads zeros here)
   if (zero_stats(ctx)) return -1;
   for (int attempt = 0; attempt < 3; ++attempt) {
-    p.rows = ctx->d_rows;
-    p.reg_cnt = ctx->d_seg;
-    p.reg_cap = ctx->rows_cap / ctx->nreg;
+    p.rows = row_words(ctx);
+    p.reg_cnt = ctx->d_seg.p;
+    p.reg_cap = ctx->d_rows.cap / ctx->nreg;
     MG_TRY(hipEventRecord(ctx->ev[8], ctx->stream));
     hipLaunchKernelGGL(k_probe_long<false>, dim3(grid), dim3(kBlock), 0, ctx->stream, p);
     MG_TRY(hipGetLastError());
@@ -4038,11 +4025,11 @@ int long_probe(mg_ctx* ctx, bool contain, uint64_t a_lo, uint64_t a_hi) {
 
 // d_super in ID order (unpermuted into d_tmp32 when the slots are clustered)
 const uint32_t* super_in_id_order(mg_ctx* ctx) {
-  if (!ctx->d_id || !ctx->n) return ctx->d_super;
-  if (ensure(ctx, &ctx->d_tmp32, &ctx->tmp32_cap, ctx->n, "d_tmp32") != hipSuccess) return ctx->d_super;
+  if (!ctx->d_id || !ctx->n) return ctx->d_super.p;
+  if (ctx->d_tmp32.ensure(ctx, ctx->n, "d_tmp32") != hipSuccess) return ctx->d_super.p;
   hipLaunchKernelGGL(k_unpermute_u32, dim3((uint32_t)((ctx->n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                     ctx->d_super, ctx->d_id, ctx->n, ctx->d_tmp32);
-  return ctx->d_tmp32;
+                     ctx->d_super.p, ctx->d_id, ctx->n, ctx->d_tmp32.p);
+  return ctx->d_tmp32.p;
 }
 
 float elapsed(hipEvent_t a, hipEvent_t b) {
@@ -4060,7 +4047,7 @@ int settle_runs(mg_ctx* ctx, bool* again) {
   *again = false;
   if (ctx->run_cnt_host.size() < ctx->nrun_reg) ctx->run_cnt_host.resize(ctx->nrun_reg);
   if (ctx->nrun_reg)
-    MG_TRY(hipMemcpyAsync(ctx->run_cnt_host.data(), ctx->d_run_cnt, ctx->nrun_reg * sizeof(unsigned long long),
+    MG_TRY(hipMemcpyAsync(ctx->run_cnt_host.data(), ctx->d_run_cnt.p, ctx->nrun_reg * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
   uint64_t run_max = 0, total = 0;
@@ -4136,23 +4123,11 @@ void mg_destroy(mg_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   (void)hipStreamSynchronize(ctx->stream);
-  void* bufs[] = {ctx->d_words, ctx->d_len, ctx->d_cells, ctx->d_superkey, ctx->d_super, ctx->d_any, ctx->d_rows,
-                  ctx->d_seg, ctx->d_stats, ctx->d_compact, ctx->d_runs, ctx->d_run_cnt, ctx->d_blk, ctx->d_flat_cnt,
-                  ctx->d_slot_cnt, ctx->d_freq, ctx->d_kb, ctx->d_ke, ctx->d_key0, ctx->d_xkk[0], ctx->d_xkk[1], ctx->d_xke[0], ctx->d_xke[1], 
-                  ctx->d_xflag, ctx->d_nlive,
-                  ctx->d_xk[0], ctx->d_xk[1], ctx->d_xv[0], ctx->d_xv[1], ctx->d_xsort_tmp,
-                  ctx->d_digest, ctx->id_store[0], ctx->id_store[1], ctx->phys_store[0], ctx->phys_store[1],
-                  ctx->d_tmp32, ctx->d_lay_k[0], ctx->d_lay_k[1], ctx->d_lay_v[0], ctx->d_lay_v[1], ctx->d_lay_tmp,
-                  ctx->d_words_alt, ctx->d_len_alt, ctx->d_cbits, ctx->d_ccnt, ctx->d_lcells, ctx->d_lkcells,
-                  ctx->d_rhead, ctx->d_rstart, ctx->d_rcnt, ctx->d_dcnt, ctx->d_p0runs, ctx->d_p0cnt, ctx->d_xexp,
-                  ctx->d_kblk, ctx->d_rdst, ctx->d_cells_alt};
-  for (void* b : bufs)
-    if (b) (void)hipFree(b);
   for (auto& e : ctx->ev)
     if (e) (void)hipEventDestroy(e);
   if (ctx->side) (void)hipStreamDestroy(ctx->side);
   if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;  // (the derived stages' arrays and events go with it: DevArray, EventPair)
+  delete ctx;  // (every device array and the stages' events go with it: DevArray, EventPair)
 }
 
 const char* mg_last_error(const mg_ctx* ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -4195,19 +4170,19 @@ int mg_upload_reads_packed(mg_ctx* ctx, const uint64_t* words, const uint16_t* l
   ctx->maxw = maxw;
   ctx->stride = slot_stride(maxw);
   const size_t nw = (size_t)(n_reads + 2) * ctx->stride + 2;  // zero pad for over-reads
-  MG_ENSURE(d_words, words_cap, nw);
-  MG_ENSURE(d_len, len_cap, n_reads + 1);
-  MG_TRY(hipMemsetAsync(ctx->d_words, 0, nw * sizeof(uint64_t), ctx->stream));
+  MG_ENSURE(d_words, nw);
+  MG_ENSURE(d_len, n_reads + 1);
+  MG_TRY(hipMemsetAsync(ctx->d_words.p, 0, nw * sizeof(uint64_t), ctx->stream));
   const uint32_t copy_w = std::min<uint32_t>(words_per_read, ctx->stride);
   if (n_reads && ctx->stride == words_per_read) {
-    MG_TRY(hipMemcpyAsync(ctx->d_words, words, n_reads * ctx->stride * sizeof(uint64_t), hipMemcpyHostToDevice,
+    MG_TRY(hipMemcpyAsync(ctx->d_words.p, words, n_reads * ctx->stride * sizeof(uint64_t), hipMemcpyHostToDevice,
                           ctx->stream));
   } else if (n_reads) {
-    MG_TRY(hipMemcpy2DAsync(ctx->d_words, ctx->stride * sizeof(uint64_t), words, words_per_read * sizeof(uint64_t),
+    MG_TRY(hipMemcpy2DAsync(ctx->d_words.p, ctx->stride * sizeof(uint64_t), words, words_per_read * sizeof(uint64_t),
                             copy_w * sizeof(uint64_t), n_reads, hipMemcpyHostToDevice, ctx->stream));
   }
   if (n_reads)
-    MG_TRY(hipMemcpyAsync(ctx->d_len, lens, n_reads * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
+    MG_TRY(hipMemcpyAsync(ctx->d_len.p, lens, n_reads * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
   ctx->n_good = n_reads;
   return finish_upload(ctx, lens);
@@ -4231,30 +4206,23 @@ int mg_upload_reads_ascii(mg_ctx* ctx, const char* concat, const uint64_t* offse
   ctx->maxw = maxw;
   ctx->stride = slot_stride(maxw);
   const uint64_t total = n_reads ? offsets[n_reads] : 0;
-  // staging buffers freed on every exit path (an error return included)
-  struct Staging {
-    char* ascii = nullptr;
-    uint64_t* off = nullptr;
-    ~Staging() {
-      if (ascii) (void)hipFree(ascii);
-      if (off) (void)hipFree(off);
-    }
-  } st;
-  MG_TRY(hipMalloc(&st.ascii, std::max<uint64_t>(total, 1)));
-  MG_TRY(hipMalloc(&st.off, (n_reads + 1) * sizeof(uint64_t)));
-  char* const d_ascii = st.ascii;
-  uint64_t* const d_off = st.off;
+  Scratch<char> ascii;
+  Scratch<uint64_t> off;
+  MG_SCRATCH(ascii, total, "upload records");
+  MG_SCRATCH(off, n_reads + 1, "upload record offsets");
+  char* const d_ascii = ascii.p;
+  uint64_t* const d_off = off.p;
   const size_t nw = (size_t)(n_reads + 2) * ctx->stride + 2;
-  MG_ENSURE(d_words, words_cap, nw);
-  MG_ENSURE(d_len, len_cap, n_reads + 1);
-  MG_TRY(hipMemsetAsync(ctx->d_words, 0, nw * sizeof(uint64_t), ctx->stream));
+  MG_ENSURE(d_words, nw);
+  MG_ENSURE(d_len, n_reads + 1);
+  MG_TRY(hipMemsetAsync(ctx->d_words.p, 0, nw * sizeof(uint64_t), ctx->stream));
   if (total) MG_TRY(hipMemcpyAsync(d_ascii, concat, total, hipMemcpyHostToDevice, ctx->stream));
   MG_TRY(hipMemcpyAsync(d_off, offsets, (n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   MG_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
   const uint64_t threads = n_reads * maxw;
   if (threads) {
     hipLaunchKernelGGL(k_pack_ascii, dim3((uint32_t)((threads + kBlock - 1) / kBlock)), dim3(kBlock), 0,
-                       ctx->stream, d_ascii, d_off, n_reads, maxw, ctx->stride, ctx->d_words, ctx->d_len);
+                       ctx->stream, d_ascii, d_off, n_reads, maxw, ctx->stride, ctx->d_words.p, ctx->d_len.p);
     MG_TRY(hipGetLastError());
   }
   MG_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
@@ -4269,9 +4237,9 @@ int mg_download_reads_packed(mg_ctx* ctx, uint64_t* words, uint16_t* lens, uint3
   MG_TRY(hipSetDevice(ctx->device));
   if (words_per_read) *words_per_read = ctx->maxw;
   if (words && ctx->n)
-    MG_TRY(hipMemcpy2D(words, ctx->maxw * sizeof(uint64_t), ctx->d_words, ctx->stride * sizeof(uint64_t),
+    MG_TRY(hipMemcpy2D(words, ctx->maxw * sizeof(uint64_t), ctx->d_words.p, ctx->stride * sizeof(uint64_t),
                        ctx->maxw * sizeof(uint64_t), ctx->n, hipMemcpyDeviceToHost));
-  if (lens && ctx->n) MG_TRY(hipMemcpy(lens, ctx->d_len, ctx->n * sizeof(uint16_t), hipMemcpyDeviceToHost));
+  if (lens && ctx->n) MG_TRY(hipMemcpy(lens, ctx->d_len.p, ctx->n * sizeof(uint16_t), hipMemcpyDeviceToHost));
   if (ctx->d_id && ctx->n && (words || lens)) {  // slots -> ID order
     std::vector<uint32_t> id(ctx->n);
     MG_TRY(hipMemcpy(id.data(), ctx->d_id, ctx->n * sizeof(uint32_t), hipMemcpyDeviceToHost));
@@ -4485,8 +4453,8 @@ int setup_index(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k, bool cells =
 int setup_cells(mg_ctx* ctx) {
   const size_t need = ctx->cell_n * kCell;
   if (!ctx->cells_double) {
-    MG_ENSURE(d_cells, cells_cap, need);
-    MG_TRY(hipMemsetAsync(ctx->d_cells, 0xFF, need * sizeof(uint64_t), ctx->stream));  // kEmpty
+    MG_ENSURE(d_cells, need);
+    MG_TRY(hipMemsetAsync(ctx->d_cells.p, 0xFF, need * sizeof(uint64_t), ctx->stream));  // kEmpty
     return 0;
   }
   // two tables (option cells_double): this build takes the one the previous
@@ -4494,19 +4462,18 @@ int setup_cells(mg_ctx* ctx) {
   // kernels; the stream waits for it), and the table it retires -- the last
   // index, which nothing reads once a new build starts -- is cleared there for
   // the next build.  The first build after a resize clears its own table.
-  if (ctx->d_cells_alt && ctx->cells_alt_clean >= need) {
-    std::swap(ctx->d_cells, ctx->d_cells_alt);
-    std::swap(ctx->cells_cap, ctx->cells_alt_cap);
+  if (ctx->d_cells_alt.p && ctx->cells_alt_clean >= need) {
+    ctx->d_cells.swap(ctx->d_cells_alt);
     MG_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev[13], 0));
   } else {
-    MG_ENSURE(d_cells, cells_cap, need);
-    MG_TRY(hipMemsetAsync(ctx->d_cells, 0xFF, need * sizeof(uint64_t), ctx->stream));  // kEmpty
+    MG_ENSURE(d_cells, need);
+    MG_TRY(hipMemsetAsync(ctx->d_cells.p, 0xFF, need * sizeof(uint64_t), ctx->stream));  // kEmpty
   }
   ctx->cells_alt_clean = 0;
-  MG_ENSURE(d_cells_alt, cells_alt_cap, need);
+  MG_ENSURE(d_cells_alt, need);
   MG_TRY(hipEventRecord(ctx->ev[12], ctx->stream));  // (every reader of the retired table is before this point)
   MG_TRY(hipStreamWaitEvent(ctx->side, ctx->ev[12], 0));
-  MG_TRY(hipMemsetAsync(ctx->d_cells_alt, 0xFF, need * sizeof(uint64_t), ctx->side));
+  MG_TRY(hipMemsetAsync(ctx->d_cells_alt.p, 0xFF, need * sizeof(uint64_t), ctx->side));
   MG_TRY(hipEventRecord(ctx->ev[13], ctx->side));
   ctx->cells_alt_clean = need;
   return 0;
@@ -4528,11 +4495,11 @@ template <int KIND>
 int route_slots(mg_ctx* ctx, PartParams pp, void* out, void* self_out, uint64_t slot, uint32_t rounds,
                 unsigned long long* counts, unsigned long long* precounted = nullptr) {
   const uint32_t grid = precounted ? (uint32_t)pp.nreg : part_grid(pp.nreg);
-  if (!precounted) MG_ENSURE(d_blk, blk_cap, (size_t)grid * ctx->nranks);
+  if (!precounted) MG_ENSURE(d_blk, (size_t)grid * ctx->nranks);
   pp.nranks = ctx->nranks;
   pp.nb_log2 = ctx->nb_log2;
   pp.n_reads = ctx->n;
-  pp.blk = precounted ? precounted : ctx->d_blk;
+  pp.blk = precounted ? precounted : ctx->d_blk.p;
   pp.out = out;
   pp.self_out = self_out;
   pp.self_rank = ctx->rank;
@@ -4553,19 +4520,13 @@ int route_slots(mg_ctx* ctx, PartParams pp, void* out, void* self_out, uint64_t 
 constexpr uint64_t kFlatRegion = 1024;  // records per routing region of a flat array (more blocks in flight)
 constexpr uint64_t kXRegion = 1024;     // records per probe region of the ordered received runs
 
-// region counts of a slot-layout buffer into *buf (grown as needed)
-int slot_regions(mg_ctx* ctx, unsigned long long** buf, size_t* cap, const unsigned long long* counts,
+// region counts of a slot-layout buffer into buf (grown as needed under the name `what`)
+int slot_regions(mg_ctx* ctx, DevArray<unsigned long long>& buf, const char* what, const unsigned long long* counts,
                  uint64_t slot, uint64_t reg, uint64_t nreg, int part = 0) {
-  if (*cap < nreg) {
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *cap = 0;
-    MG_TRY(hipMalloc(buf, nreg * sizeof(unsigned long long)));
-    *cap = nreg;
-  }
+  MG_GROW(buf, nreg, what);
   if (nreg)
     hipLaunchKernelGGL(k_slot_regions, dim3((uint32_t)((nreg + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       *buf, counts, slot, reg, nreg, ctx->nranks, part, ctx->rank);
+                       buf.p, counts, slot, reg, nreg, ctx->nranks, part, ctx->rank);
   MG_TRY(hipGetLastError());
   return 0;
 }
@@ -4595,11 +4556,11 @@ struct LaunchXchgKeys {
     ctx->keys_counted = false;
     unsigned long long* kblk = nullptr;
     if (ctx->nranks > 1 && nreg && ctx->nranks <= kMaxRanks) {
-      MG_ENSURE(d_kblk, kblk_cap, nreg * ctx->nranks);
-      MG_TRY(hipMemsetAsync(ctx->d_kblk, 0, nreg * ctx->nranks * sizeof(unsigned long long), ctx->stream));
-      kblk = ctx->d_kblk;
+      MG_ENSURE(d_kblk, nreg * ctx->nranks);
+      MG_TRY(hipMemsetAsync(ctx->d_kblk.p, 0, nreg * ctx->nranks * sizeof(unsigned long long), ctx->stream));
+      kblk = ctx->d_kblk.p;
     }
-    hipLaunchKernelGGL((k_xchg_keys<W>), dim3(grid), dim3(kBlock), 0, ctx->stream, p, lo, hi, ctx->d_kb, ctx->d_ke,
+    hipLaunchKernelGGL((k_xchg_keys<W>), dim3(grid), dim3(kBlock), 0, ctx->stream, p, lo, hi, ctx->d_kb.p, ctx->d_ke.p,
                        kblk, ctx->nranks);
     if (hipGetLastError() != hipSuccess) return -1;
     ctx->keys_counted = kblk != nullptr;
@@ -4626,28 +4587,15 @@ struct LaunchProbeSlots {
                  bool append = false) {
     const DiscGeom g = disc_geom<W>(ctx, contain, std::max<uint64_t>(1, ctx->n / ctx->nranks));
     const uint32_t* sup =
-        (!contain && ctx->contained_done && ctx->super_any && !ctx->runs_live) ? ctx->d_super : nullptr;
+        (!contain && ctx->contained_done && ctx->super_any && !ctx->runs_live) ? ctx->d_super.p : nullptr;
     return LaunchProbe<W>::run(ctx, contain, runs, ctx->xruns_cnt, reg, nregions, g.grid, sup, 0, 0, append);
   }
 };
 
 int ensure_rows(mg_ctx* ctx, uint64_t nsrc) {
-  const uint64_t max_regions = (uint64_t)ctx->max_blocks * kWavesPerBlock;
-  if (ctx->seg_cap_regions < max_regions) {
-    if (ctx->d_seg) (void)hipFree(ctx->d_seg);
-    ctx->d_seg = nullptr;
-    ctx->seg_cap_regions = 0;
-    if (ctx_malloc(ctx, (void**)&ctx->d_seg, max_regions * sizeof(unsigned long long), "d_seg")) return -1;
-    ctx->seg_cap_regions = max_regions;
-  }
-  const uint64_t want = ctx->rows_cap_opt ? ctx->rows_cap_opt : std::max<uint64_t>(1u << 20, 48 * nsrc);
-  if (want > ctx->rows_cap) {
-    if (ctx->d_rows) (void)hipFree(ctx->d_rows);
-    ctx->d_rows = nullptr;
-    ctx->rows_cap = 0;
-    if (ctx_malloc(ctx, (void**)&ctx->d_rows, want * 3 * sizeof(uint32_t), "d_rows (row regions)")) return -1;
-    ctx->rows_cap = want;
-  }
+  MG_ENSURE(d_seg, (uint64_t)ctx->max_blocks * kWavesPerBlock);
+  MG_GROW(ctx->d_rows, ctx->rows_cap_opt ? ctx->rows_cap_opt : std::max<uint64_t>(1u << 20, 48 * nsrc),
+          "d_rows (row regions)");
   return 0;
 }
 
@@ -4657,8 +4605,8 @@ int ensure_rows(mg_ctx* ctx, uint64_t nsrc) {
 // appended second part of a split exchange probe continues the first.)
 int zero_stats(mg_ctx* ctx) {
   if (!ctx->stats) return 0;
-  if (!ctx->d_stats) MG_TRY(hipMalloc(&ctx->d_stats, (kSegs * 4 + 1) * sizeof(unsigned long long)));
-  MG_TRY(hipMemsetAsync(ctx->d_stats, 0, (kSegs * 4 + 1) * sizeof(unsigned long long), ctx->stream));
+  MG_ENSURE(d_stats, kSegs * 4 + 1);
+  MG_TRY(hipMemsetAsync(ctx->d_stats.p, 0, (kSegs * 4 + 1) * sizeof(unsigned long long), ctx->stream));
   return 0;
 }
 
@@ -4668,7 +4616,7 @@ int settle_rows(mg_ctx* ctx, bool* again) {
   *again = false;
   if (ctx->seg_host.size() < ctx->nreg) ctx->seg_host.resize(ctx->nreg);
   if (ctx->nreg)
-    MG_TRY(hipMemcpyAsync(ctx->seg_host.data(), ctx->d_seg, ctx->nreg * sizeof(unsigned long long),
+    MG_TRY(hipMemcpyAsync(ctx->seg_host.data(), ctx->d_seg.p, ctx->nreg * sizeof(unsigned long long),
                           hipMemcpyDeviceToHost, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
   uint64_t row_max = 0, rows = 0;
@@ -4676,14 +4624,9 @@ int settle_rows(mg_ctx* ctx, bool* again) {
     row_max = std::max<uint64_t>(row_max, ctx->seg_host[r]);
     rows += ctx->seg_host[r];
   }
-  const uint64_t reg_cap = ctx->nreg ? ctx->rows_cap / ctx->nreg : 0;
+  const uint64_t reg_cap = ctx->nreg ? ctx->d_rows.cap / ctx->nreg : 0;
   if (row_max > reg_cap) {
-    const uint64_t want = (row_max + row_max / 4 + 1024) * ctx->nreg;
-    if (ctx->d_rows) (void)hipFree(ctx->d_rows);
-    ctx->d_rows = nullptr;
-    ctx->rows_cap = 0;
-    if (ctx_malloc(ctx, (void**)&ctx->d_rows, want * 3 * sizeof(uint32_t), "d_rows (row regions)")) return -1;
-    ctx->rows_cap = want;
+    MG_GROW(ctx->d_rows, (row_max + row_max / 4 + 1024) * ctx->nreg, "d_rows (row regions)");
     ++ctx->row_reruns;
     *again = true;
     return 0;
@@ -4695,7 +4638,7 @@ int settle_rows(mg_ctx* ctx, bool* again) {
 void read_stats(mg_ctx* ctx, uint64_t nsrc) {
   if (!ctx->stats) return;
   std::vector<unsigned long long> st(kSegs * 4 + 1);
-  if (hipMemcpy(st.data(), ctx->d_stats, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) !=
+  if (hipMemcpy(st.data(), ctx->d_stats.p, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost) !=
       hipSuccess)
     return;
   uint64_t acc[4] = {0, 0, 0, 0};
@@ -4787,8 +4730,8 @@ struct LaunchProbeShared {
     const DiscGeom g = disc_geom<W>(ctx, contain, std::max<uint64_t>(ctx->n, 1));
     // (after k_live_runs every run's source is uncontained: no per-run check)
     const uint32_t* sup =
-        (!contain && ctx->contained_done && ctx->super_any && !ctx->runs_live) ? ctx->d_super : nullptr;
-    return LaunchProbe<W>::run(ctx, contain, ctx->d_runs, ctx->d_run_cnt, ctx->run_cap, ctx->nrun_reg, g.grid, sup);
+        (!contain && ctx->contained_done && ctx->super_any && !ctx->runs_live) ? ctx->d_super.p : nullptr;
+    return LaunchProbe<W>::run(ctx, contain, ctx->d_runs.p, ctx->d_run_cnt.p, ctx->run_cap, ctx->nrun_reg, g.grid, sup);
   }
 };
 
@@ -4808,16 +4751,16 @@ int build_live_index(mg_ctx* ctx) {
   while (nbl < 31 && (1ull << nbl) * kCell < 5 * live) nbl++;
   if (nbl >= ctx->nb_log2 && !force) return 0;  // no smaller than the full table: probe that
   nbl = std::min(nbl, ctx->nb_log2);
-  MG_ENSURE(d_lcells, lcells_cap, (1ull << nbl) * kCell);
-  MG_TRY(hipMemsetAsync(ctx->d_lcells, 0xFF, (1ull << nbl) * kCell * sizeof(uint64_t), ctx->stream));
+  MG_ENSURE(d_lcells, (1ull << nbl) * kCell);
+  MG_TRY(hipMemsetAsync(ctx->d_lcells.p, 0xFF, (1ull << nbl) * kCell * sizeof(uint64_t), ctx->stream));
   IndexParams p = index_params(ctx);
   p.nb_log2 = nbl;
   p.rank = 0;
   p.nranks = 1;
   p.cell_lo = 0;
   p.cell_n = 1ull << nbl;
-  p.cells = ctx->d_lcells;
-  p.cbits = ctx->d_cbits;
+  p.cells = ctx->d_lcells.p;
+  p.cbits = ctx->d_cbits.p;
   if (dispatch_w<LaunchIndexLive>(ctx->maxw, ctx, &p)) return launch_fail(ctx, "live index launch failed");
   ctx->lnb_log2 = nbl;
   ctx->live_cells = 1ull << nbl;
@@ -4826,41 +4769,27 @@ int build_live_index(mg_ctx* ctx) {
   return 0;
 }
 
-// the sort / scan scratch of the exchange build (d_xsort_tmp), grown to tb bytes
-hipError_t grow_tmp(mg_ctx* ctx, size_t tb) {
-  if (tb > ctx->xsort_tmp_cap) {
-    if (ctx->d_xsort_tmp) {
-      const hipError_t e = hipFree(ctx->d_xsort_tmp);
-      if (e != hipSuccess) return e;
-    }
-    ctx->d_xsort_tmp = nullptr;
-    ctx->xsort_tmp_cap = 0;
-    const hipError_t e = ctx_malloc(ctx, &ctx->d_xsort_tmp, tb, "d_xsort_tmp (sort scratch)");
-    if (e != hipSuccess) return e;
-    ctx->xsort_tmp_cap = tb;
-  }
-  return hipSuccess;
-}
+// the name of d_xsort_tmp, the sort / scan / select scratch of the exchange build, in its messages
+constexpr char kXsortTmp[] = "d_xsort_tmp (sort scratch)";
 
 // option check_cells: fail the build when a filed record cannot be walked to
 int check_cells(mg_ctx* ctx, const uint32_t* key, const uint64_t* ent, const uint32_t* start,
                 const unsigned long long* n_dev, uint64_t n_host, const uint64_t* cells, uint64_t cell_n,
                 uint32_t gshift, uint32_t cshift, int skip_odd) {
   if (!ctx->check_cells || !n_host) return 0;
-  unsigned long long* d_bad = nullptr;
-  MG_TRY(hipMalloc(&d_bad, 33 * sizeof(unsigned long long)));
-  MG_TRY(hipMemsetAsync(d_bad, 0, 33 * sizeof(unsigned long long), ctx->stream));
+  Scratch<unsigned long long> bad;
+  MG_SCRATCH(bad, 33, "check_cells report");
+  MG_TRY(hipMemsetAsync(bad.p, 0, 33 * sizeof(unsigned long long), ctx->stream));
   hipLaunchKernelGGL(k_check_cells, dim3((uint32_t)std::min<uint64_t>((n_host + kBlock - 1) / kBlock, 4096)),
                      dim3(kBlock), 0, ctx->stream, key, ent, start, n_dev, n_host, gshift, cshift, skip_odd, cells,
-                     cell_n, d_bad);
+                     cell_n, bad.p);
   unsigned long long h[33];
-  MG_TRY(hipMemcpyAsync(h, d_bad, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  MG_TRY(hipMemcpyAsync(h, bad.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(d_bad);
   std::string scan_note;
   if (start && n_host <= (1u << 22)) {  // the max-scan against the host's
     std::vector<uint32_t> hh(n_host), hs(n_host);
-    MG_TRY(hipMemcpy(hh.data(), ctx->d_rhead, n_host * 4, hipMemcpyDeviceToHost));
+    MG_TRY(hipMemcpy(hh.data(), ctx->d_rhead.p, n_host * 4, hipMemcpyDeviceToHost));
     MG_TRY(hipMemcpy(hs.data(), start, n_host * 4, hipMemcpyDeviceToHost));
     uint32_t mx = 0;
     uint64_t heads = 0, bad_scan = 0, first_bad = 0;
@@ -4910,22 +4839,22 @@ int build_cells(mg_ctx* ctx, const uint32_t* key, const uint64_t* ent, const uns
     return check_cells(ctx, key, ent, nullptr, n_dev, n_host, cells, cell_n, gshift, cshift, skip_odd);
   }
   if (n_host > 0xFFFFFFFFull) return set_err(ctx, "cell build: more than 2^32 records");
-  MG_ENSURE(d_rhead, rhead_cap, n_host);
-  MG_ENSURE(d_rstart, rstart_cap, n_host);
+  MG_ENSURE(d_rhead, n_host);
+  MG_ENSURE(d_rstart, n_host);
   hipLaunchKernelGGL(k_over_heads, dim3(grid), dim3(kBlock), 0, ctx->stream, key, ent, n_dev, n_host, gshift, skip_odd,
-                     ctx->d_rhead);
+                     ctx->d_rhead.p);
   MG_TRY(hipGetLastError());
   size_t tb = 0;
-  MG_TRY(rocprim::inclusive_scan(nullptr, tb, ctx->d_rhead, ctx->d_rstart, (size_t)n_host,
+  MG_TRY(rocprim::inclusive_scan(nullptr, tb, ctx->d_rhead.p, ctx->d_rstart.p, (size_t)n_host,
                                  rocprim::maximum<uint32_t>(), ctx->stream));
-  MG_TRY(grow_tmp(ctx, tb));
-  tb = ctx->xsort_tmp_cap;
-  MG_TRY(rocprim::inclusive_scan(ctx->d_xsort_tmp, tb, ctx->d_rhead, ctx->d_rstart, (size_t)n_host,
+  MG_GROW(ctx->d_xsort_tmp, tb, kXsortTmp);
+  tb = ctx->d_xsort_tmp.cap;
+  MG_TRY(rocprim::inclusive_scan(ctx->d_xsort_tmp.p, tb, ctx->d_rhead.p, ctx->d_rstart.p, (size_t)n_host,
                                  rocprim::maximum<uint32_t>(), ctx->stream));
-  hipLaunchKernelGGL(k_cells_place, dim3(grid), dim3(kBlock), 0, ctx->stream, key, ent, ctx->d_rstart, n_dev, n_host,
+  hipLaunchKernelGGL(k_cells_place, dim3(grid), dim3(kBlock), 0, ctx->stream, key, ent, ctx->d_rstart.p, n_dev, n_host,
                      gshift, cshift, skip_odd, cells, cell_n);
   MG_TRY(hipGetLastError());
-  return check_cells(ctx, key, ent, ctx->d_rstart, n_dev, n_host, cells, cell_n, gshift, cshift, skip_odd);
+  return check_cells(ctx, key, ent, ctx->d_rstart.p, n_dev, n_host, cells, cell_n, gshift, cshift, skip_odd);
 }
 
 // The exchange mode's discovery index (option live_index): after
@@ -4950,34 +4879,34 @@ int build_live_index_xchg(mg_ctx* ctx) {
     ++sft;
   if (!sft && !force) return 0;  // no smaller than the full table: probe that
   const uint64_t live_n = (ctx->cell_n + (1ull << sft) - 1) >> sft;
-  MG_ENSURE(d_lcells, lcells_cap, live_n * kCell);
+  MG_ENSURE(d_lcells, live_n * kCell);
   // the live reads' records, compacted in order into the sort's other buffers
   const uint64_t n = ctx->xkeys_n;
   uint32_t* lk = ctx->xkey_k_alt;
   uint64_t* le = ctx->xkey_e_alt;
-  MG_ENSURE(d_xflag, xflag_cap, std::max<uint64_t>(n, 1));
-  if (!ctx->d_nlive) MG_TRY(hipMalloc(&ctx->d_nlive, sizeof(unsigned long long)));
-  MG_TRY(hipMemsetAsync(ctx->d_nlive, 0, sizeof(unsigned long long), ctx->stream));
+  MG_ENSURE(d_xflag, std::max<uint64_t>(n, 1));
+  MG_ENSURE(d_nlive, 1);
+  MG_TRY(hipMemsetAsync(ctx->d_nlive.p, 0, sizeof(unsigned long long), ctx->stream));
   if (n) {
     hipLaunchKernelGGL(k_live_flags, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       ctx->xkey_e, n, ctx->d_cbits, ctx->d_xflag);
+                       ctx->xkey_e, n, ctx->d_cbits.p, ctx->d_xflag.p);
     MG_TRY(hipGetLastError());
     for (int pass = 0; pass < 2; ++pass) {
       size_t tb = 0;
-      MG_TRY(pass ? hipcub::DeviceSelect::Flagged(nullptr, tb, ctx->xkey_e, ctx->d_xflag, le, ctx->d_nlive, (int)n,
+      MG_TRY(pass ? hipcub::DeviceSelect::Flagged(nullptr, tb, ctx->xkey_e, ctx->d_xflag.p, le, ctx->d_nlive.p, (int)n,
                                                   ctx->stream)
-                  : hipcub::DeviceSelect::Flagged(nullptr, tb, ctx->xkey_k, ctx->d_xflag, lk, ctx->d_nlive, (int)n,
+                  : hipcub::DeviceSelect::Flagged(nullptr, tb, ctx->xkey_k, ctx->d_xflag.p, lk, ctx->d_nlive.p, (int)n,
                                                   ctx->stream));
-      MG_TRY(grow_tmp(ctx, tb));
-      tb = ctx->xsort_tmp_cap;
-      MG_TRY(pass ? hipcub::DeviceSelect::Flagged(ctx->d_xsort_tmp, tb, ctx->xkey_e, ctx->d_xflag, le, ctx->d_nlive,
+      MG_GROW(ctx->d_xsort_tmp, tb, kXsortTmp);
+      tb = ctx->d_xsort_tmp.cap;
+      MG_TRY(pass ? hipcub::DeviceSelect::Flagged(ctx->d_xsort_tmp.p, tb, ctx->xkey_e, ctx->d_xflag.p, le, ctx->d_nlive.p,
                                                   (int)n, ctx->stream)
-                  : hipcub::DeviceSelect::Flagged(ctx->d_xsort_tmp, tb, ctx->xkey_k, ctx->d_xflag, lk, ctx->d_nlive,
+                  : hipcub::DeviceSelect::Flagged(ctx->d_xsort_tmp.p, tb, ctx->xkey_k, ctx->d_xflag.p, lk, ctx->d_nlive.p,
                                                   (int)n, ctx->stream));
     }
   }
   const uint32_t lsh = sft + ctx->xkey_cls + ctx->xkey_fs;  // (classes merged)
-  if (build_cells(ctx, lk, le, ctx->d_nlive, n, ctx->d_lcells, live_n, lsh, lsh, 0, ctx->xkey_par)) return -1;
+  if (build_cells(ctx, lk, le, ctx->d_nlive.p, n, ctx->d_lcells.p, live_n, lsh, lsh, 0, ctx->xkey_par)) return -1;
   ctx->live_shift = sft;
   ctx->live_cells = live_n;
   ctx->live_coarse = true;
@@ -5004,7 +4933,7 @@ int live_runs_launch(mg_ctx* ctx, ulonglong2* runs, unsigned long long* cnt, uin
     st = ctx->side;
     *on_side = true;
   }
-  hipLaunchKernelGGL(k_live_runs, dim3(grid), dim3(kBlock), 0, st, runs, cnt, cap, nreg, ctx->d_cbits);
+  hipLaunchKernelGGL(k_live_runs, dim3(grid), dim3(kBlock), 0, st, runs, cnt, cap, nreg, ctx->d_cbits.p);
   MG_TRY(hipGetLastError());
   if (*on_side) MG_TRY(hipEventRecord(ctx->ev[11], ctx->side));
   return 0;
@@ -5026,7 +4955,7 @@ int probe_shared(mg_ctx* ctx, bool contain) {
     MG_TRY(hipEventRecord(ctx->ev[8], ctx->stream));
     bool side = false;
     if (!contain && ctx->contained_done && ctx->super_any && !ctx->runs_live && ctx->nrun_reg && ctx->live_runs) {
-      if (live_runs_launch(ctx, ctx->d_runs, ctx->d_run_cnt, ctx->run_cap, ctx->nrun_reg, &side)) return -1;
+      if (live_runs_launch(ctx, ctx->d_runs.p, ctx->d_run_cnt.p, ctx->run_cap, ctx->nrun_reg, &side)) return -1;
       ctx->runs_live = true;
     }
     if (!contain && attempt == 0 && ctx->contained_done && build_live_index(ctx)) return -1;
@@ -5070,8 +4999,8 @@ static int sort_xrecs(mg_ctx* ctx, const ulonglong2* recv, uint64_t slot, uint32
   for (uint32_t s = 0; s < P; ++s) n += std::min<uint64_t>(c[s], (uint64_t)rounds * slot);  // cut streams: what arrived
   if (n > 0x7FFFFFFFull) return set_err(ctx, "exchange: more than 2^31 records received on one rank");
   for (int b = 0; b < 2; ++b) {
-    MG_ENSURE(d_xk[b], xk_cap[b], std::max<uint64_t>(n, 1));
-    MG_ENSURE(d_xv[b], xv_cap[b], std::max<uint64_t>(n, 1));
+    MG_ENSURE(d_xk[b], std::max<uint64_t>(n, 1));
+    MG_ENSURE(d_xv[b], std::max<uint64_t>(n, 1));
   }
   int hb = 1;
   while (hb < 40 && (1ULL << hb) < ctx->cell_n) ++hb;  // bits of a local bucket index
@@ -5081,7 +5010,7 @@ static int sort_xrecs(mg_ctx* ctx, const ulonglong2* recv, uint64_t slot, uint32
     const uint64_t total = (uint64_t)rounds * P * slot;
     const uint32_t grid = (uint32_t)std::min<uint64_t>((total + kBlock - 1) / kBlock, 65536);
     hipLaunchKernelGGL(k_xruns_keys, dim3(grid), dim3(kBlock), 0, ctx->stream, recv, slot, P, total, counts,
-                       (1ULL << ctx->nb_log2) - 1, ctx->cell_lo, shift, ctx->d_xk[0], ctx->d_xv[0]);
+                       (1ULL << ctx->nb_log2) - 1, ctx->cell_lo, shift, ctx->d_xk[0].p, ctx->d_xv[0].p);
     MG_TRY(hipGetLastError());
     // one rank: its one stream is its own scan's runs in scan order, which the
     // fused path probes unsorted (the clustered layout's locality); a bucket
@@ -5091,20 +5020,14 @@ static int sort_xrecs(mg_ctx* ctx, const ulonglong2* recv, uint64_t slot, uint32
       *n_out = n;
       return 0;
     }
-    rocprim::double_buffer<uint32_t> keys(ctx->d_xk[0], ctx->d_xk[1]);
-    rocprim::double_buffer<ulonglong2> vals(ctx->d_xv[0], ctx->d_xv[1]);
+    rocprim::double_buffer<uint32_t> keys(ctx->d_xk[0].p, ctx->d_xk[1].p);
+    rocprim::double_buffer<ulonglong2> vals(ctx->d_xv[0].p, ctx->d_xv[1].p);
     size_t tb = 0;
     MG_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, vals, (unsigned int)n, 0u, 8u, ctx->stream));
-    if (tb > ctx->xsort_tmp_cap) {
-      if (ctx->d_xsort_tmp) MG_TRY(hipFree(ctx->d_xsort_tmp));
-      ctx->d_xsort_tmp = nullptr;
-      ctx->xsort_tmp_cap = 0;
-      if (ctx_malloc(ctx, &ctx->d_xsort_tmp, tb, "d_xsort_tmp (sort scratch)")) return -1;
-      ctx->xsort_tmp_cap = tb;
-    }
-    tb = ctx->xsort_tmp_cap;
-    MG_TRY(rocprim::radix_sort_pairs(ctx->d_xsort_tmp, tb, keys, vals, (unsigned int)n, 0u, 8u, ctx->stream));
-    ctx->xv_sel = vals.current() == ctx->d_xv[0] ? 0 : 1;
+    MG_GROW(ctx->d_xsort_tmp, tb, kXsortTmp);
+    tb = ctx->d_xsort_tmp.cap;
+    MG_TRY(rocprim::radix_sort_pairs(ctx->d_xsort_tmp.p, tb, keys, vals, (unsigned int)n, 0u, 8u, ctx->stream));
+    ctx->xv_sel = vals.current() == ctx->d_xv[0].p ? 0 : 1;
   }
   *n_out = n;
   return 0;
@@ -5117,10 +5040,10 @@ static int sort_xruns(mg_ctx* ctx, const ulonglong2* recv, uint64_t slot, uint32
   uint64_t n = 0;
   if (sort_xrecs(ctx, recv, slot, rounds, counts, &n)) return -1;
   const uint64_t nreg = (n + kXRegion - 1) / kXRegion;
-  MG_ENSURE(d_flat_cnt, flat_cnt_cap, std::max<uint64_t>(nreg, 1));
+  MG_ENSURE(d_flat_cnt, std::max<uint64_t>(nreg, 1));
   if (nreg)
     hipLaunchKernelGGL(k_fixed_regions, dim3((uint32_t)((nreg + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream,
-                       ctx->d_flat_cnt, n, kXRegion, nreg);
+                       ctx->d_flat_cnt.p, n, kXRegion, nreg);
   MG_TRY(hipGetLastError());
   ctx->xruns_n = n;
   ctx->xruns_ready = true;
@@ -5142,8 +5065,8 @@ static int sort_xruns(mg_ctx* ctx, const ulonglong2* recv, uint64_t slot, uint32
 static int prepare_xruns(mg_ctx* ctx, const void* recv8, uint64_t slot, uint32_t rounds,
                          const unsigned long long* counts, int part = 0) {
   if (ctx->nranks == 1) {  // one rank: the scan's own run regions, as the fused path probes them
-    ctx->xruns_base = ctx->d_runs;
-    ctx->xruns_cnt = ctx->d_run_cnt;
+    ctx->xruns_base = ctx->d_runs.p;
+    ctx->xruns_cnt = ctx->d_run_cnt.p;
     ctx->xruns_reg = ctx->run_cap;
     ctx->xruns_nreg = ctx->nrun_reg;
     ctx->xruns_ready = true;
@@ -5153,15 +5076,15 @@ static int prepare_xruns(mg_ctx* ctx, const void* recv8, uint64_t slot, uint32_t
   // mix64, re-hashed from this rank's copy of the read) in the context's own
   // buffer, same slot positions, so the slot regions below apply unchanged
   const uint64_t total = (uint64_t)rounds * ctx->nranks * slot;
-  MG_ENSURE(d_xexp, xexp_cap, std::max<uint64_t>(total, 1));
+  MG_ENSURE(d_xexp, std::max<uint64_t>(total, 1));
   if (total && dispatch_w<LaunchXrunsExpand>(ctx->maxw, ctx, reinterpret_cast<const uint64_t*>(recv8), slot, rounds,
-                                             counts, ctx->d_xexp, part))
+                                             counts, ctx->d_xexp.p, part))
     return launch_fail(ctx, "run records launch failed");
-  const void* recv = ctx->d_xexp;
+  const void* recv = ctx->d_xexp.p;
   if (ctx->xchg_sort_runs) {  // (never split: mg_xchg_probe_own leaves the step whole then)
     if (sort_xruns(ctx, reinterpret_cast<const ulonglong2*>(recv), slot, rounds, counts)) return -1;
-    ctx->xruns_cnt = ctx->d_flat_cnt;  // (after sort_xruns: it may have grown the counts)
-    ctx->xruns_base = ctx->d_xv[ctx->xv_sel];
+    ctx->xruns_cnt = ctx->d_flat_cnt.p;  // (after sort_xruns: it may have grown the counts)
+    ctx->xruns_base = ctx->d_xv[ctx->xv_sel].p;
     ctx->xruns_reg = kXRegion;
     ctx->xruns_nreg = (ctx->xruns_n + kXRegion - 1) / kXRegion;
     return 0;
@@ -5174,8 +5097,8 @@ static int prepare_xruns(mg_ctx* ctx, const void* recv8, uint64_t slot, uint32_t
   const uint64_t K = slot ? slot / reg : 0;
   const uint64_t nreg = (uint64_t)rounds * ctx->nranks * K;
   // (part 1 reads only this rank's entry of the send counts; part 2 the received counts)
-  if (slot_regions(ctx, &ctx->d_flat_cnt, &ctx->flat_cnt_cap, counts, slot, reg, nreg, part)) return -1;
-  ctx->xruns_cnt = ctx->d_flat_cnt;
+  if (slot_regions(ctx, ctx->d_flat_cnt, "d_flat_cnt", counts, slot, reg, nreg, part)) return -1;
+  ctx->xruns_cnt = ctx->d_flat_cnt.p;
   ctx->xruns_base = reinterpret_cast<ulonglong2*>(const_cast<void*>(recv));
   ctx->xruns_reg = reg;
   // a split probe walks only its part's regions (LaunchProbe maps them, ProbeParams::rm_*)
@@ -5205,66 +5128,57 @@ int layout_current(mg_ctx* ctx, bool force) {
   int pb = 1;
   while (pb < 10 && (1u << pb) <= ctx->maxlen) ++pb;  // offsets < maxlen (capped at 10 bits)
   for (int b = 0; b < 2; ++b) {
-    MG_ENSURE(d_lay_k[b], lay_k_cap[b], n);
-    MG_ENSURE(d_lay_v[b], lay_v_cap[b], n);
+    MG_ENSURE(d_lay_k[b], n);
+    MG_ENSURE(d_lay_v[b], n);
   }
   const unsigned kbits = 32u + (unsigned)pb + (grouped ? 2u : 0u);  // the key's significant bits
   size_t tb = 0;
-  MG_TRY(rocprim::radix_sort_pairs(nullptr, tb, ctx->d_lay_k[0], ctx->d_lay_k[1], ctx->d_lay_v[0], ctx->d_lay_v[1],
+  MG_TRY(rocprim::radix_sort_pairs(nullptr, tb, ctx->d_lay_k[0].p, ctx->d_lay_k[1].p, ctx->d_lay_v[0].p, ctx->d_lay_v[1].p,
                                    (unsigned int)n, 0u, kbits, ctx->stream));
-  if (tb > ctx->lay_tmp_cap) {
-    if (ctx->d_lay_tmp) MG_TRY(hipFree(ctx->d_lay_tmp));
-    ctx->d_lay_tmp = nullptr;
-    ctx->lay_tmp_cap = 0;
-    if (ctx_malloc(ctx, &ctx->d_lay_tmp, tb, "d_lay_tmp (layout sort scratch)")) return -1;
-    ctx->lay_tmp_cap = tb;
-  }
-  tb = ctx->lay_tmp_cap;
-  MG_ENSURE(d_words_alt, words_alt_cap, ctx->words_cap);
-  MG_ENSURE(d_len_alt, len_alt_cap, ctx->len_cap);
+  MG_GROW(ctx->d_lay_tmp, tb, "d_lay_tmp (layout sort scratch)");
+  tb = ctx->d_lay_tmp.cap;
+  MG_ENSURE(d_words_alt, ctx->d_words.cap);
+  MG_ENSURE(d_len_alt, ctx->d_len.cap);
   // the new maps go to the pair the current order does not use
-  const int sel = (ctx->d_id && ctx->d_id == ctx->id_store[0]) ? 1 : 0;
-  MG_ENSURE(id_store[sel], id_cap[sel], n);
-  MG_ENSURE(phys_store[sel], phys_cap[sel], n);
-  uint32_t* id_new = ctx->id_store[sel];
-  uint32_t* ph_new = ctx->phys_store[sel];
+  const int sel = (ctx->d_id && ctx->d_id == ctx->id_store[0].p) ? 1 : 0;
+  MG_ENSURE(id_store[sel], n);
+  MG_ENSURE(phys_store[sel], n);
+  uint32_t* id_new = ctx->id_store[sel].p;
+  uint32_t* ph_new = ctx->phys_store[sel].p;
   const uint64_t S = slot_words((int)ctx->maxw);
   // --- timed: kernels only
   MG_TRY(hipEventRecord(ctx->ev[14], ctx->stream));
-  if (dispatch_w<LaunchLayout>(ctx->maxw, ctx, lo, hi, grouped, pb, ctx->d_lay_k[0], ctx->d_lay_v[0]))
+  if (dispatch_w<LaunchLayout>(ctx->maxw, ctx, lo, hi, grouped, pb, ctx->d_lay_k[0].p, ctx->d_lay_v[0].p))
     return launch_fail(ctx, "layout key launch failed");
-  MG_TRY(rocprim::radix_sort_pairs(ctx->d_lay_tmp, tb, ctx->d_lay_k[0], ctx->d_lay_k[1], ctx->d_lay_v[0],
-                                   ctx->d_lay_v[1], (unsigned int)n, 0u, kbits, ctx->stream));
-  if (dispatch_w<LaunchLayoutGather>(ctx->maxw, ctx, ctx->d_lay_v[1], ctx->d_words_alt, ctx->d_len_alt, id_new))
+  MG_TRY(rocprim::radix_sort_pairs(ctx->d_lay_tmp.p, tb, ctx->d_lay_k[0].p, ctx->d_lay_k[1].p, ctx->d_lay_v[0].p,
+                                   ctx->d_lay_v[1].p, (unsigned int)n, 0u, kbits, ctx->stream));
+  if (dispatch_w<LaunchLayoutGather>(ctx->maxw, ctx, ctx->d_lay_v[1].p, ctx->d_words_alt.p, ctx->d_len_alt.p, id_new))
     return launch_fail(ctx, "layout gather launch failed");
   // the zero pad past the last slot (over-reads of the kernels)
-  MG_TRY(hipMemsetAsync(ctx->d_words_alt + n * S, 0, (ctx->words_cap - n * S) * sizeof(uint64_t), ctx->stream));
+  MG_TRY(hipMemsetAsync(ctx->d_words_alt.p + n * S, 0, (ctx->d_words.cap - n * S) * sizeof(uint64_t), ctx->stream));
   hipLaunchKernelGGL(k_layout_phys, dim3((uint32_t)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, ctx->stream, id_new,
                      n, ph_new);
   MG_TRY(hipGetLastError());
   MG_TRY(hipEventRecord(ctx->ev[15], ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
   // --- commit
-  std::swap(ctx->d_words, ctx->d_words_alt);
-  std::swap(ctx->words_cap, ctx->words_alt_cap);
-  std::swap(ctx->d_len, ctx->d_len_alt);
-  std::swap(ctx->len_cap, ctx->len_alt_cap);
+  ctx->d_words.swap(ctx->d_words_alt);
+  ctx->d_len.swap(ctx->d_len_alt);
   ctx->d_id = id_new;
   ctx->d_phys = ph_new;
   ctx->layout_lo = grouped ? lo : 0;
   ctx->layout_hi = grouped ? hi : 0;
   ctx->t.layout_ms = elapsed(ctx->ev[14], ctx->ev[15]);
   if (!ctx->layout_scratch) {  // (option layout_scratch = 0: many contexts on one device, the simulated ranks)
-    for (void** b : {(void**)&ctx->d_words_alt, (void**)&ctx->d_len_alt, (void**)&ctx->d_lay_k[0], (void**)&ctx->d_lay_k[1],
-                     (void**)&ctx->d_lay_v[0], (void**)&ctx->d_lay_v[1], &ctx->d_lay_tmp,
-                     (void**)&ctx->id_store[1 - sel], (void**)&ctx->phys_store[1 - sel]})
-      if (*b) {
-        MG_TRY(hipFree(*b));
-        *b = nullptr;
-      }
-    ctx->words_alt_cap = ctx->len_alt_cap = ctx->lay_tmp_cap = 0;
-    ctx->lay_k_cap[0] = ctx->lay_k_cap[1] = ctx->lay_v_cap[0] = ctx->lay_v_cap[1] = 0;
-    ctx->id_cap[1 - sel] = ctx->phys_cap[1 - sel] = 0;
+    ctx->d_words_alt.release();
+    ctx->d_len_alt.release();
+    ctx->d_lay_k[0].release();
+    ctx->d_lay_k[1].release();
+    ctx->d_lay_v[0].release();
+    ctx->d_lay_v[1].release();
+    ctx->d_lay_tmp.release();
+    ctx->id_store[1 - sel].release();
+    ctx->phys_store[1 - sel].release();
   }
   return 0;
 }
@@ -5299,7 +5213,7 @@ int mg_build_index(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k) {
   if (ensure_layout_range(ctx)) return -1;  // a source-read range set after the upload
   // the cell table exists before the timed window (its clear is inside it)
   if (setup_index(ctx, min_overlap, seed_k, false)) return -1;
-  MG_ENSURE(d_cells, cells_cap, ctx->cell_n * kCell);
+  MG_ENSURE(d_cells, ctx->cell_n * kCell);
   MG_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
   if (setup_cells(ctx)) return -1;
   ctx->scan_state = 0;
@@ -5326,8 +5240,8 @@ int mg_build_index(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k) {
     // the discovery probe then walks the live reads' table (always built,
     // build_live_index), so this table holds o = 0 / 2 only
     ctx->index_o3 = !(ctx->key0_ready && ctx->live_index);
-    if (ctx->key0_ready && ctx->prefix_probe) MG_ENSURE(d_p0runs, p0runs_cap, ctx->n + 1);
-    if (ctx->key0_ready && !ctx->prefix_probe) MG_ENSURE(d_key0, key0_cap, ctx->n + 1);
+    if (ctx->key0_ready && ctx->prefix_probe) MG_ENSURE(d_p0runs, ctx->n + 1);
+    if (ctx->key0_ready && !ctx->prefix_probe) MG_ENSURE(d_key0, ctx->n + 1);
     if (ctx->n && dispatch_w<LaunchScanAll>(ctx->maxw, ctx, ctx->stream))
       return launch_fail(ctx, "index build launch failed");
     if (!ctx->n) ctx->nrun_reg = 0;
@@ -5347,23 +5261,20 @@ int mg_mark_contained(mg_ctx* ctx, uint32_t* super_out) {
   ctx->err.clear();  // (a message left by an earlier failed call is not this call's cause)
   MG_TRY(hipSetDevice(ctx->device));
   if (!ctx->index_ready) return set_err(ctx, "mg_build_index must run first");
-  const uint32_t* super_was = ctx->d_super;
-  MG_ENSURE(d_super, super_cap, ctx->n + 1);
-  if (ctx->d_super != super_was) ctx->super_zero_n = 0;  // (a new buffer: nothing known about it)
-  MG_ENSURE(d_cbits, cbits_cap, (ctx->n + 63) / 64 * 2);
-  if (!ctx->d_any) MG_TRY(hipMalloc(&ctx->d_any, sizeof(unsigned int)));
+  const uint32_t* super_was = ctx->d_super.p;
+  MG_ENSURE(d_super, ctx->n + 1);
+  if (ctx->d_super.p != super_was) ctx->super_zero_n = 0;  // (a new buffer: nothing known about it)
+  MG_ENSURE(d_cbits, (ctx->n + 63) / 64 * 2);
+  MG_ENSURE(d_any, 1);
   ctx->t.contained_ms = 0.f;
   if (ctx->minlen != ctx->maxlen) {  // OverlapGraph.cpp:228-233
-    MG_ENSURE(d_superkey, superkey_cap, ctx->n + 1);
-    ctx->superkey = ctx->d_superkey;
-    MG_TRY(hipMemsetAsync(ctx->d_superkey, 0, (ctx->n + 1) * sizeof(unsigned long long), ctx->stream));
-    MG_TRY(hipMemsetAsync(ctx->d_any, 0, sizeof(unsigned int), ctx->stream));
-    if (!ctx->d_ccnt) MG_TRY(hipMalloc(&ctx->d_ccnt, 64 * 16 * sizeof(unsigned int)));
-    MG_TRY(hipMemsetAsync(ctx->d_ccnt, 0, 64 * 16 * sizeof(unsigned int), ctx->stream));
-    if (ctx->stats) {  // containment work counters (mg_counters c_*)
-      if (!ctx->d_stats) MG_TRY(hipMalloc(&ctx->d_stats, (kSegs * 4 + 1) * sizeof(unsigned long long)));
-      MG_TRY(hipMemsetAsync(ctx->d_stats, 0, (kSegs * 4 + 1) * sizeof(unsigned long long), ctx->stream));
-    }
+    MG_ENSURE(d_superkey, ctx->n + 1);
+    ctx->superkey = ctx->d_superkey.p;
+    MG_TRY(hipMemsetAsync(ctx->d_superkey.p, 0, (ctx->n + 1) * sizeof(unsigned long long), ctx->stream));
+    MG_TRY(hipMemsetAsync(ctx->d_any.p, 0, sizeof(unsigned int), ctx->stream));
+    MG_ENSURE(d_ccnt, 64 * 16);
+    MG_TRY(hipMemsetAsync(ctx->d_ccnt.p, 0, 64 * 16 * sizeof(unsigned int), ctx->stream));
+    if (zero_stats(ctx)) return -1;  // containment work counters (mg_counters c_*)
     MG_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
     // sharded contexts still need the full superReadID vector: run over all
     // buckets (the containment pass is small, only for mixed lengths)
@@ -5378,14 +5289,14 @@ int mg_mark_contained(mg_ctx* ctx, uint32_t* super_out) {
     }
     if (ctx->n)
       hipLaunchKernelGGL(k_super_finalize, dim3(super_grid(ctx)), dim3(kBlock), 0,
-                         ctx->stream, ctx->d_superkey, ctx->n, ctx->d_super, ctx->d_any, ctx->d_cbits, ctx->d_ccnt);
+                         ctx->stream, ctx->d_superkey.p, ctx->n, ctx->d_super.p, ctx->d_any.p, ctx->d_cbits.p, ctx->d_ccnt.p);
     ctx->super_zero_n = 0;
     MG_TRY(hipGetLastError());
     MG_TRY(hipEventRecord(ctx->ev[3], ctx->stream));
     unsigned int any = 0;
     unsigned int ccnt[64 * 16];
-    MG_TRY(hipMemcpyAsync(&any, ctx->d_any, sizeof(any), hipMemcpyDeviceToHost, ctx->stream));
-    MG_TRY(hipMemcpyAsync(ccnt, ctx->d_ccnt, sizeof(ccnt), hipMemcpyDeviceToHost, ctx->stream));
+    MG_TRY(hipMemcpyAsync(&any, ctx->d_any.p, sizeof(any), hipMemcpyDeviceToHost, ctx->stream));
+    MG_TRY(hipMemcpyAsync(ccnt, ctx->d_ccnt.p, sizeof(ccnt), hipMemcpyDeviceToHost, ctx->stream));
     MG_TRY(hipStreamSynchronize(ctx->stream));
     ctx->t.contained_ms = elapsed(ctx->ev[2], ctx->ev[3]);
     ctx->super_any = any != 0;
@@ -5394,7 +5305,7 @@ int mg_mark_contained(mg_ctx* ctx, uint32_t* super_out) {
     ctx->live_ready = false;
     if (ctx->stats) {
       std::vector<unsigned long long> st(kSegs * 4 + 1);
-      MG_TRY(hipMemcpy(st.data(), ctx->d_stats, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+      MG_TRY(hipMemcpy(st.data(), ctx->d_stats.p, st.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
       uint64_t acc[4] = {0, 0, 0, 0};
       for (int s2 = 0; s2 < kSegs; ++s2)
         for (int i = 0; i < 4; ++i) acc[i] += st[s2 * 4 + i];
@@ -5407,7 +5318,7 @@ int mg_mark_contained(mg_ctx* ctx, uint32_t* super_out) {
     // every superReadID 0 (one read length: nothing is contained); the memset
     // only when a finalize or a new buffer left other values
     if (ctx->super_zero_n < ctx->n + 1) {
-      MG_TRY(hipMemsetAsync(ctx->d_super, 0, (ctx->n + 1) * sizeof(uint32_t), ctx->stream));
+      MG_TRY(hipMemsetAsync(ctx->d_super.p, 0, (ctx->n + 1) * sizeof(uint32_t), ctx->stream));
       ctx->super_zero_n = ctx->n + 1;
     }
     ctx->super_any = false;
@@ -5514,7 +5425,7 @@ int mg_xchg_begin(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k) {
   MG_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
   if (setup_index(ctx, min_overlap, seed_k, false)) return -1;
   // this rank's cells: mg_xchg_insert_keys writes every one of them (no clear)
-  MG_ENSURE(d_cells, cells_cap, ctx->cell_n * kCell);
+  MG_ENSURE(d_cells, ctx->cell_n * kCell);
   ctx->xchg = true;
   ctx->row_reruns = ctx->run_reruns = 0;  // (a new step)
   ctx->probe_vsplit = 1;
@@ -5530,8 +5441,8 @@ int mg_xchg_begin(mg_ctx* ctx, uint32_t min_overlap, uint32_t seed_k) {
   source_range(ctx, &lo, &hi);
   ctx->xchg_lo = lo;
   ctx->xchg_hi = hi;
-  MG_ENSURE(d_kb, kb_cap, 4 * (hi - lo) + 1);
-  MG_ENSURE(d_ke, ke_cap, 4 * (hi - lo) + 1);
+  MG_ENSURE(d_kb, 4 * (hi - lo) + 1);
+  MG_ENSURE(d_ke, 4 * (hi - lo) + 1);
   ctx->scan_state = 0;
   ctx->shared_scan_ms = 0.f;
   ctx->t = mg_timings{};
@@ -5590,38 +5501,38 @@ int mg_xchg_pack(mg_ctx* ctx, int what, void* dst, uint64_t slot, uint32_t round
     pp.cap = kFlatRegion;
     pp.flat_n = (ctx->index_o1 ? 4 : 3) * nsrc;  // (no o = 1 keys: the last segment is holes, key_seg)
     pp.nreg = (pp.flat_n + kFlatRegion - 1) / kFlatRegion;
-    pp.key_bk = ctx->d_kb;
-    pp.key_ent = ctx->d_ke;
+    pp.key_bk = ctx->d_kb.p;
+    pp.key_ent = ctx->d_ke.p;
     pp.key_n = nsrc;  // (key o of source a - xchg_lo at o * nsrc + a - xchg_lo)
     pp.a_lo = 0;
     pp.nsrc = nsrc;
     if (ctx->keys_counted && pp.nreg)  // k_xchg_keys counted them per (region, rank): no count pass
-      return route_slots<OWN_KEY>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_kblk);
+      return route_slots<OWN_KEY>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_kblk.p);
     return route_slots<OWN_KEY>(ctx, pp, dst, self_dst, slot, rounds, cnt);
   }
   if (what == MG_RUNS) {  // the scan's run regions, each run to its bucket's owner
     PartParams pp{};
-    pp.base = ctx->d_runs;
+    pp.base = ctx->d_runs.p;
     pp.cap = ctx->run_cap;
-    pp.cnt = ctx->d_run_cnt;
+    pp.cnt = ctx->d_run_cnt.p;
     pp.nreg = ctx->nrun_reg;
     if (ctx->runs_meta8) {  // (the keys-first receiver scan: 8-B metas + owner bytes, counted per rank)
-      pp.dst8 = ctx->d_rdst;
+      pp.dst8 = ctx->d_rdst.p;
       if (ctx->runs_counted && pp.nreg)
-        return route_slots<OWN_META>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_rcnt);
+        return route_slots<OWN_META>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_rcnt.p);
       return route_slots<OWN_META>(ctx, pp, dst, self_dst, slot, rounds, cnt);
     }
     if (ctx->runs_counted && pp.nreg)  // the scan counted them per rank: one block per region, no count pass
-      return route_slots<OWN_BUCKET>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_rcnt);
+      return route_slots<OWN_BUCKET>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_rcnt.p);
     return route_slots<OWN_BUCKET>(ctx, pp, dst, self_dst, slot, rounds, cnt);
   }
   PartParams pp{};
-  pp.base = ctx->d_rows;
-  pp.cap = ctx->nreg ? ctx->rows_cap / ctx->nreg : 0;
-  pp.cnt = ctx->d_seg;
+  pp.base = row_words(ctx);
+  pp.cap = ctx->nreg ? ctx->d_rows.cap / ctx->nreg : 0;
+  pp.cnt = ctx->d_seg.p;
   pp.nreg = ctx->n_rows ? ctx->nreg : 0;
   if (ctx->rows_counted && pp.nreg)  // the probe counted them per rank: no count pass
-    return route_slots<OWN_SRC>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_dcnt);
+    return route_slots<OWN_SRC>(ctx, pp, dst, self_dst, slot, rounds, cnt, ctx->d_dcnt.p);
   return route_slots<OWN_SRC>(ctx, pp, dst, self_dst, slot, rounds, cnt);
 }
 
@@ -5688,10 +5599,10 @@ int mg_xchg_insert_keys(mg_ctx* ctx, const void* recv, uint64_t slot, uint32_t r
     // one rank: its own key records are the input (mg_xchg_pack packed nothing);
     // without o = 1 keys they are the first three segments (key_seg)
     n = (ctx->index_o1 ? 4 : 3) * (ctx->xchg_hi - ctx->xchg_lo);
-    k0 = ctx->d_kb;
-    e0 = ctx->d_ke;
-    MG_ENSURE(d_xkk[1], xkk_cap[1], std::max<uint64_t>(n, 1));
-    MG_ENSURE(d_xke[1], xke_cap[1], std::max<uint64_t>(n, 1));
+    k0 = ctx->d_kb.p;
+    e0 = ctx->d_ke.p;
+    MG_ENSURE(d_xkk[1], std::max<uint64_t>(n, 1));
+    MG_ENSURE(d_xke[1], std::max<uint64_t>(n, 1));
   } else {
     const uint64_t total = (uint64_t)rounds * P * slot;
     if (total) {
@@ -5702,17 +5613,17 @@ int mg_xchg_insert_keys(mg_ctx* ctx, const void* recv, uint64_t slot, uint32_t r
       for (uint32_t q = 0; q < P; ++q) n += std::min<uint64_t>(c[q], (uint64_t)rounds * slot);  // cut streams: what arrived
     }
     for (int b = 0; b < 2; ++b) {
-      MG_ENSURE(d_xkk[b], xkk_cap[b], std::max<uint64_t>(n, 1));
-      MG_ENSURE(d_xke[b], xke_cap[b], std::max<uint64_t>(n, 1));
+      MG_ENSURE(d_xkk[b], std::max<uint64_t>(n, 1));
+      MG_ENSURE(d_xke[b], std::max<uint64_t>(n, 1));
     }
-    k0 = ctx->d_xkk[0];
-    e0 = ctx->d_xke[0];
+    k0 = ctx->d_xkk[0].p;
+    e0 = ctx->d_xke[0].p;
   }
   if (n > 0x7FFFFFFFull) return set_err(ctx, "exchange: more than 2^31 key records on one rank");
   ctx->xkey_k = k0;
   ctx->xkey_e = e0;
-  ctx->xkey_k_alt = ctx->d_xkk[1];
-  ctx->xkey_e_alt = ctx->d_xke[1];
+  ctx->xkey_k_alt = ctx->d_xkk[1].p;
+  ctx->xkey_e_alt = ctx->d_xke[1].p;
   int hb = 0;
   while (hb < 32 && (1ull << hb) < ctx->cell_n) ++hb;  // bits of a local cell index
   ctx->xkey_cls = (!ctx->index_o3 && hb < 31) ? 1 : 0;
@@ -5740,20 +5651,20 @@ int mg_xchg_insert_keys(mg_ctx* ctx, const void* recv, uint64_t slot, uint32_t r
   }
   hb += (int)fs;
   if (hb > 0 && n > 1) {  // a cell's records consecutive
-    rocprim::double_buffer<uint32_t> keys(k0, ctx->d_xkk[1]);
-    rocprim::double_buffer<uint64_t> vals(e0, ctx->d_xke[1]);
+    rocprim::double_buffer<uint32_t> keys(k0, ctx->d_xkk[1].p);
+    rocprim::double_buffer<uint64_t> vals(e0, ctx->d_xke[1].p);
     size_t tb = 0;
     MG_TRY(rocprim::radix_sort_pairs(nullptr, tb, keys, vals, (unsigned int)n, 0u, (unsigned)hb, ctx->stream));
-    MG_TRY(grow_tmp(ctx, tb));
-    tb = ctx->xsort_tmp_cap;
-    MG_TRY(rocprim::radix_sort_pairs(ctx->d_xsort_tmp, tb, keys, vals, (unsigned int)n, 0u, (unsigned)hb, ctx->stream));
+    MG_GROW(ctx->d_xsort_tmp, tb, kXsortTmp);
+    tb = ctx->d_xsort_tmp.cap;
+    MG_TRY(rocprim::radix_sort_pairs(ctx->d_xsort_tmp.p, tb, keys, vals, (unsigned int)n, 0u, (unsigned)hb, ctx->stream));
     ctx->xkey_k = keys.current();
     ctx->xkey_e = vals.current();
     ctx->xkey_k_alt = keys.alternate();
     ctx->xkey_e_alt = vals.alternate();
   }
   ctx->xkeys_n = n;
-  if (build_cells(ctx, ctx->xkey_k, ctx->xkey_e, nullptr, n, ctx->d_cells, ctx->cell_n, fs, fs + ctx->xkey_cls,
+  if (build_cells(ctx, ctx->xkey_k, ctx->xkey_e, nullptr, n, ctx->d_cells.p, ctx->cell_n, fs, fs + ctx->xkey_cls,
                   ctx->xkey_cls, ctx->xkey_par))
     return -1;
   MG_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
@@ -5844,8 +5755,8 @@ int mg_xchg_probe(mg_ctx* ctx, int contain, const void* recv, uint64_t slot, uin
     if (split && attempt == 1) {  // a rerun probes every stream in one launch
       ctx->xruns_part = 0;
       nregions = (uint64_t)rounds * ctx->nranks * ctx->xruns_K;
-      if (slot_regions(ctx, &ctx->d_flat_cnt, &ctx->flat_cnt_cap, reinterpret_cast<const unsigned long long*>(counts),
-                       slot, reg, nregions, 0))
+      if (slot_regions(ctx, ctx->d_flat_cnt, "d_flat_cnt", reinterpret_cast<const unsigned long long*>(counts), slot,
+                       reg, nregions, 0))
         return -1;
     }
     if (!(split && attempt == 0)) MG_TRY(hipEventRecord(ctx->ev[4], ctx->stream));  // (split: at the own part)
@@ -5952,8 +5863,8 @@ int mg_begin_contained(mg_ctx* ctx, void* superkey, int* needed) {
     if (superkey) {
       ctx->superkey = reinterpret_cast<unsigned long long*>(superkey);
     } else {
-      MG_ENSURE(d_superkey, superkey_cap, ctx->n + 1);
-      ctx->superkey = ctx->d_superkey;
+      MG_ENSURE(d_superkey, ctx->n + 1);
+      ctx->superkey = ctx->d_superkey.p;
     }
     MG_TRY(hipMemsetAsync(ctx->superkey, 0, ctx->n * sizeof(unsigned long long), ctx->stream));
   }
@@ -5964,25 +5875,25 @@ int mg_finalize_contained(mg_ctx* ctx, uint32_t* super_out) {
   if (!ctx) return -1;
   ctx->err.clear();  // (a message left by an earlier failed call is not this call's cause)
   MG_TRY(hipSetDevice(ctx->device));
-  const uint32_t* super_was = ctx->d_super;
-  MG_ENSURE(d_super, super_cap, ctx->n + 1);
-  if (ctx->d_super != super_was) ctx->super_zero_n = 0;  // (a new buffer: nothing known about it)
-  MG_ENSURE(d_cbits, cbits_cap, (ctx->n + 63) / 64 * 2);
-  if (!ctx->d_any) MG_TRY(hipMalloc(&ctx->d_any, sizeof(unsigned int)));
+  const uint32_t* super_was = ctx->d_super.p;
+  MG_ENSURE(d_super, ctx->n + 1);
+  if (ctx->d_super.p != super_was) ctx->super_zero_n = 0;  // (a new buffer: nothing known about it)
+  MG_ENSURE(d_cbits, (ctx->n + 63) / 64 * 2);
+  MG_ENSURE(d_any, 1);
   ctx->super_any = false;
   if (ctx->minlen != ctx->maxlen && ctx->superkey) {
-    MG_TRY(hipMemsetAsync(ctx->d_any, 0, sizeof(unsigned int), ctx->stream));
-    if (!ctx->d_ccnt) MG_TRY(hipMalloc(&ctx->d_ccnt, 64 * 16 * sizeof(unsigned int)));
-    MG_TRY(hipMemsetAsync(ctx->d_ccnt, 0, 64 * 16 * sizeof(unsigned int), ctx->stream));
+    MG_TRY(hipMemsetAsync(ctx->d_any.p, 0, sizeof(unsigned int), ctx->stream));
+    MG_ENSURE(d_ccnt, 64 * 16);
+    MG_TRY(hipMemsetAsync(ctx->d_ccnt.p, 0, 64 * 16 * sizeof(unsigned int), ctx->stream));
     if (ctx->n)
       hipLaunchKernelGGL(k_super_finalize, dim3(super_grid(ctx)), dim3(kBlock), 0,
-                         ctx->stream, ctx->superkey, ctx->n, ctx->d_super, ctx->d_any, ctx->d_cbits, ctx->d_ccnt);
+                         ctx->stream, ctx->superkey, ctx->n, ctx->d_super.p, ctx->d_any.p, ctx->d_cbits.p, ctx->d_ccnt.p);
     ctx->super_zero_n = 0;
     MG_TRY(hipGetLastError());
     unsigned int any = 0;
     unsigned int ccnt[64 * 16];
-    MG_TRY(hipMemcpyAsync(&any, ctx->d_any, sizeof(any), hipMemcpyDeviceToHost, ctx->stream));
-    MG_TRY(hipMemcpyAsync(ccnt, ctx->d_ccnt, sizeof(ccnt), hipMemcpyDeviceToHost, ctx->stream));
+    MG_TRY(hipMemcpyAsync(&any, ctx->d_any.p, sizeof(any), hipMemcpyDeviceToHost, ctx->stream));
+    MG_TRY(hipMemcpyAsync(ccnt, ctx->d_ccnt.p, sizeof(ccnt), hipMemcpyDeviceToHost, ctx->stream));
     MG_TRY(hipStreamSynchronize(ctx->stream));
     ctx->super_any = any != 0;
     ctx->n_contained = 0;
@@ -5991,7 +5902,7 @@ int mg_finalize_contained(mg_ctx* ctx, uint32_t* super_out) {
     // every superReadID 0 (one read length: nothing is contained); the memset
     // only when a finalize or a new buffer left other values
     if (ctx->super_zero_n < ctx->n + 1) {
-      MG_TRY(hipMemsetAsync(ctx->d_super, 0, (ctx->n + 1) * sizeof(uint32_t), ctx->stream));
+      MG_TRY(hipMemsetAsync(ctx->d_super.p, 0, (ctx->n + 1) * sizeof(uint32_t), ctx->stream));
       ctx->super_zero_n = ctx->n + 1;
     }
   }
@@ -6016,23 +5927,22 @@ int mg_copy_rows(mg_ctx* ctx, mg_edge* out, uint64_t cap, uint64_t* n_copied) {
   if (n_copied) *n_copied = 0;
   if (!ctx->nreg || !ctx->n_rows) return 0;
   // gather the per-wavefront regions into one contiguous array, then one copy
-  const uint64_t reg_cap = ctx->rows_cap / ctx->nreg;
+  const uint64_t reg_cap = ctx->d_rows.cap / ctx->nreg;
   std::vector<uint64_t> prefix(ctx->nreg + 1, 0);
   for (uint64_t r = 0; r < ctx->nreg; ++r)
     prefix[r + 1] = prefix[r] + std::min<uint64_t>(ctx->seg_host[r], reg_cap);
   const uint64_t total = prefix[ctx->nreg];
-  uint64_t* d_prefix = nullptr;
-  MG_TRY(hipMalloc(&d_prefix, prefix.size() * sizeof(uint64_t)));
-  MG_TRY(hipMemcpyAsync(d_prefix, prefix.data(), prefix.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
+  Scratch<uint64_t> d_prefix;
+  MG_SCRATCH(d_prefix, prefix.size(), "row region offsets");
+  MG_TRY(hipMemcpyAsync(d_prefix.p, prefix.data(), prefix.size() * sizeof(uint64_t), hipMemcpyHostToDevice,
                         ctx->stream));
-  MG_ENSURE(d_compact, compact_cap, total * 3);
-  hipLaunchKernelGGL(k_compact_rows, dim3((uint32_t)ctx->nreg), dim3(kBlock), 0, ctx->stream, ctx->d_rows, reg_cap,
-                     d_prefix, ctx->d_compact);
+  MG_ENSURE(d_compact, total * 3);
+  hipLaunchKernelGGL(k_compact_rows, dim3((uint32_t)ctx->nreg), dim3(kBlock), 0, ctx->stream, row_words(ctx), reg_cap,
+                     d_prefix.p, ctx->d_compact.p);
   MG_TRY(hipGetLastError());
   const uint64_t c = std::min(cap, total);
-  if (c) MG_TRY(hipMemcpyAsync(out, ctx->d_compact, c * sizeof(mg_edge), hipMemcpyDeviceToHost, ctx->stream));
+  if (c) MG_TRY(hipMemcpyAsync(out, ctx->d_compact.p, c * sizeof(mg_edge), hipMemcpyDeviceToHost, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
-  (void)hipFree(d_prefix);
   if (n_copied) *n_copied = c;
   return 0;
 }
@@ -6047,9 +5957,9 @@ int mg_lookup_key(mg_ctx* ctx, const char* key, uint32_t key_len, uint64_t* out,
   if (ctx->nranks > 1) return set_err(ctx, "lookup on a bucket-sharded index");
   if ((!ctx->index_o1 || !ctx->index_o3) && !long_mode(ctx) && !ctx->lookup_ready) {
     // the step's index has no o = 1 keys: file all four once into the lookup table
-    MG_ENSURE(d_lkcells, lkcells_cap, ctx->cell_n * kCell);
-    MG_TRY(hipMemsetAsync(ctx->d_lkcells, 0xFF, ctx->cell_n * kCell * sizeof(uint64_t), ctx->stream));
-    if (ctx->n && dispatch_w<LaunchIndex>(ctx->maxw, ctx, ctx->d_lkcells, true))
+    MG_ENSURE(d_lkcells, ctx->cell_n * kCell);
+    MG_TRY(hipMemsetAsync(ctx->d_lkcells.p, 0xFF, ctx->cell_n * kCell * sizeof(uint64_t), ctx->stream));
+    if (ctx->n && dispatch_w<LaunchIndex>(ctx->maxw, ctx, ctx->d_lkcells.p, true))
       return set_err(ctx, "lookup table build failed");
     ctx->lookup_ready = true;
   }
@@ -6067,25 +5977,22 @@ int mg_lookup_key(mg_ctx* ctx, const char* key, uint32_t key_len, uint64_t* out,
     }
     q[i >> 5] |= code << (62 - 2 * (i & 31));
   }
-  uint64_t* dq = nullptr;
-  unsigned long long* dout = nullptr;
-  unsigned int* dn = nullptr;
+  Scratch<uint64_t> dq;
+  Scratch<unsigned long long> dout;
+  Scratch<unsigned int> dn;
   const uint32_t dcap = (uint32_t)std::min<uint64_t>(std::max<uint64_t>(cap, 1), 1u << 24);
-  MG_TRY(hipMalloc(&dq, (qwords + 1) * sizeof(uint64_t)));
-  MG_TRY(hipMalloc(&dout, dcap * sizeof(unsigned long long)));
-  MG_TRY(hipMalloc(&dn, sizeof(unsigned int)));
-  MG_TRY(hipMemcpyAsync(dq, q.data(), (qwords + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  MG_TRY(hipMemsetAsync(dn, 0, sizeof(unsigned int), ctx->stream));
-  if (launch_lookup(ctx, dq, qwords, dout, dcap, dn)) return set_err(ctx, "lookup failed");
+  MG_SCRATCH(dq, qwords + 1, "lookup key");
+  MG_SCRATCH(dout, dcap, "lookup results");
+  MG_SCRATCH(dn, 1, "lookup count");
+  MG_TRY(hipMemcpyAsync(dq.p, q.data(), (qwords + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  MG_TRY(hipMemsetAsync(dn.p, 0, sizeof(unsigned int), ctx->stream));
+  if (launch_lookup(ctx, dq.p, qwords, dout.p, dcap, dn.p)) return set_err(ctx, "lookup failed");
   unsigned int n = 0;
-  MG_TRY(hipMemcpyAsync(&n, dn, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
+  MG_TRY(hipMemcpyAsync(&n, dn.p, sizeof(n), hipMemcpyDeviceToHost, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
   std::vector<unsigned long long> res(std::min<uint32_t>(n, dcap));
   if (!res.empty())
-    MG_TRY(hipMemcpy(res.data(), dout, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  (void)hipFree(dq);
-  (void)hipFree(dout);
-  (void)hipFree(dn);
+    MG_TRY(hipMemcpy(res.data(), dout.p, res.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   // reference list order: insertion order = ID ascending, then o (HashTable.cpp:58-60, 98-101)
   std::sort(res.begin(), res.end(), [](unsigned long long x, unsigned long long y) {
     const uint64_t ix = x & 0x3FFFFFFFFFFFFFFFULL, iy = y & 0x3FFFFFFFFFFFFFFFULL;
@@ -6097,15 +6004,15 @@ int mg_lookup_key(mg_ctx* ctx, const char* key, uint32_t key_len, uint64_t* out,
 }
 
 static int digest_begin(mg_ctx* ctx) {
-  if (!ctx->d_digest) MG_TRY(hipMalloc(&ctx->d_digest, 4 * sizeof(unsigned long long)));
-  MG_TRY(hipMemsetAsync(ctx->d_digest, 0, 4 * sizeof(unsigned long long), ctx->stream));
+  MG_ENSURE(d_digest, 4);
+  MG_TRY(hipMemsetAsync(ctx->d_digest.p, 0, 4 * sizeof(unsigned long long), ctx->stream));
   return 0;
 }
 
 static int digest_end(mg_ctx* ctx, uint64_t* out) {
   MG_TRY(hipGetLastError());
   unsigned long long h[4];
-  MG_TRY(hipMemcpyAsync(h, ctx->d_digest, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
+  MG_TRY(hipMemcpyAsync(h, ctx->d_digest.p, sizeof(h), hipMemcpyDeviceToHost, ctx->stream));
   MG_TRY(hipStreamSynchronize(ctx->stream));
   for (int i = 0; i < 4; ++i) out[i] = h[i];
   return 0;
@@ -6120,10 +6027,10 @@ int mg_rows_digest(mg_ctx* ctx, const void* rows, uint64_t n_rows, uint64_t* out
     if (n_rows)
       hipLaunchKernelGGL(k_rows_digest, dim3(grid), dim3(kBlock), 0, ctx->stream,
                          reinterpret_cast<const uint32_t*>(rows), (uint64_t)0, nullptr, (uint64_t)0, n_rows,
-                         ctx->d_digest);
+                         ctx->d_digest.p);
   } else if (ctx->nreg && ctx->n_rows) {
-    hipLaunchKernelGGL(k_rows_digest, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->d_rows,
-                       ctx->rows_cap / ctx->nreg, ctx->d_seg, ctx->nreg, (uint64_t)0, ctx->d_digest);
+    hipLaunchKernelGGL(k_rows_digest, dim3(grid), dim3(kBlock), 0, ctx->stream, row_words(ctx),
+                       ctx->d_rows.cap / ctx->nreg, ctx->d_seg.p, ctx->nreg, (uint64_t)0, ctx->d_digest.p);
   }
   return digest_end(ctx, out);
 }
@@ -6136,13 +6043,13 @@ int mg_slots_digest(mg_ctx* ctx, const void* rows, uint64_t slot, uint32_t round
   const uint64_t nreg = (uint64_t)rounds * ctx->nranks;
   if (nreg && slot) {
     if (!rows || !counts) return set_err(ctx, "mg_slots_digest: null buffer");
-    if (slot_regions(ctx, &ctx->d_slot_cnt, &ctx->slot_cnt_cap, reinterpret_cast<const unsigned long long*>(counts),
-                     slot, slot, nreg))
+    if (slot_regions(ctx, ctx->d_slot_cnt, "d_slot_cnt", reinterpret_cast<const unsigned long long*>(counts), slot,
+                     slot, nreg))
       return -1;
     const uint32_t grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(4096, ((uint64_t)ctx->n_cu) * 8));
     hipLaunchKernelGGL(k_rows_digest, dim3(grid), dim3(kBlock), 0, ctx->stream,
-                       reinterpret_cast<const uint32_t*>(rows), slot, ctx->d_slot_cnt, nreg, (uint64_t)0,
-                       ctx->d_digest);
+                       reinterpret_cast<const uint32_t*>(rows), slot, ctx->d_slot_cnt.p, nreg, (uint64_t)0,
+                       ctx->d_digest.p);
     MG_TRY(hipGetLastError());
   }
   return digest_end(ctx, out);
@@ -6155,7 +6062,7 @@ int mg_super_digest(mg_ctx* ctx, uint64_t* out) {
   if (digest_begin(ctx)) return -1;
   if (ctx->super_any && ctx->n) {
     const uint32_t grid = (uint32_t)std::min<uint64_t>(4096, (ctx->n + kBlock - 1) / kBlock);
-    hipLaunchKernelGGL(k_super_digest, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->d_super, ctx->n, ctx->d_digest, ctx->d_id);
+    hipLaunchKernelGGL(k_super_digest, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->d_super.p, ctx->n, ctx->d_digest.p, ctx->d_id);
   }
   return digest_end(ctx, out);
 }

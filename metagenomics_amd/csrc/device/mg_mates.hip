@@ -261,7 +261,7 @@ int lookup(mg_ctx* ctx, const char* concat, const uint64_t* offsets, uint64_t n_
 }
 
 int have_reads(mg_ctx* ctx, const char* who) {
-  if (ctx->n && (!ctx->d_words || !ctx->d_len)) return set_err(ctx, std::string(who) + ": no reads on the device");
+  if (ctx->n && (!ctx->d_words.p || !ctx->d_len.p)) return set_err(ctx, std::string(who) + ": no reads on the device");
   return 0;
 }
 
@@ -318,7 +318,7 @@ int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets
   if (have_reads(ctx, "mg_build_mate_pairs")) return -1;
   if (use_super) {
     if (whole_multiset(ctx, "mg_build_mate_pairs (use_super)")) return -1;
-    if (!ctx->index_ready || !ctx->contained_done || !ctx->d_super)
+    if (!ctx->index_ready || !ctx->contained_done || !ctx->d_super.p)
       return set_err(ctx, "mg_build_mate_pairs: use_super needs a completed mg_mark_contained for the current reads");
   }
   hipStream_t st = ctx->stream;
@@ -365,7 +365,7 @@ int mg_build_mate_pairs(mg_ctx* ctx, const char* concat, const uint64_t* offsets
   if (n_raw) {
     hipLaunchKernelGGL(k_mate_emit, dim3(blocks_for(n_pairs)), dim3(kThreads), 0, st, view_of(ctx), q.canon.p, q.len.p,
                        q.valid.p, q.fwd.p, q.ids.p, n_pairs, q.cw, d_ds.p, n_datasets,
-                       use_super ? (const uint32_t*)ctx->d_super : (const uint32_t*)nullptr, owner.p, mate.p, od.p,
+                       use_super ? (const uint32_t*)ctx->d_super.p : (const uint32_t*)nullptr, owner.p, mate.p, od.p,
                        ctl.p);
     MG_TRY(hipGetLastError());
     // (dataset, orient), then (owner, mate): stable, so a run of equal records is in sequence order

@@ -277,7 +277,7 @@ int mg_build_placements(mg_ctx* ctx, const mg_contig_edge* edges, uint64_t n_edg
     return set_err(ctx, "mg_build_placements: null argument");
   MG_TRY(hipSetDevice(ctx->device));
   if (whole_multiset(ctx, "mg_build_placements")) return -1;
-  if (ctx->n && !ctx->d_len) return set_err(ctx, "mg_build_placements: no reads on the device");
+  if (ctx->n && !ctx->d_len.p) return set_err(ctx, "mg_build_placements: no reads on the device");
   if (n_edges >> 31) return set_err(ctx, "mg_build_placements: 2^31 or more edges are not supported");
   std::vector<uint64_t> ebase;
   if (edge_bases(ctx, "mg_build_placements", edges, n_edges, n_list, 0, ebase)) return -1;
@@ -441,7 +441,7 @@ int mg_edge_coverage(mg_ctx* ctx, const uint32_t* freq, uint64_t* out, float* de
   PlaceStage& pl = ctx->places;
   const uint64_t n_edges = pl.edges.size(), E = pl.n, N = ctx->n;
   if (n_edges && !out) return set_err(ctx, "mg_edge_coverage: null argument");
-  if (!freq && !(ctx->freq_ready && ctx->d_freq))
+  if (!freq && !(ctx->freq_ready && ctx->d_freq.p))
     return set_err(ctx, "mg_edge_coverage: no resident frequencies (the reads were not ingested on the device): "
                         "pass freq");
   for (uint64_t k = 0; k < n_edges; ++k)
@@ -454,7 +454,7 @@ int mg_edge_coverage(mg_ctx* ctx, const uint32_t* freq, uint64_t* out, float* de
   Scratch<ull> d_fsum, ctl, d_out, delta;
   Scratch<uint64_t> d_cbase, cov;
   Scratch<uint8_t> tmp;
-  const uint32_t* fp = ctx->d_freq;
+  const uint32_t* fp = ctx->d_freq.p;
   if (freq) {
     MG_SCRATCH(d_f, N, "caller's read frequencies");
     if (N) MG_TRY(hipMemcpyAsync(d_f.p, freq, N * sizeof(uint32_t), hipMemcpyHostToDevice, st));

@@ -1,10 +1,10 @@
 // mg_stage.hpp — INTERNAL: what the derived-stage translation units share
 // beyond the context (mg_dataset.hip, mg_disc.hip, mg_comp.hip, mg_mates.hip,
-// mg_contigs.hip, mg_places.hip): call-lifetime scratch, the view of the
-// resident reads, the launch grid, the CSR starts of sorted owners, control
-// words, the copy tail of the mg_copy_* calls and the edge lists that
-// mg_build_contigs and mg_build_placements both take.  mg_kernels.hip does not
-// include it.
+// mg_contigs.hip, mg_places.hip): the view of the resident reads, the launch
+// grid, the CSR starts of sorted owners, control words, the copy tail of the
+// mg_copy_* calls and the edge lists that mg_build_contigs and
+// mg_build_placements both take.  (DevArray, Scratch and their growth macros
+// are in mg_ctx.hpp.)  mg_kernels.hip does not include it.
 #ifndef MG_STAGE_HPP_
 #define MG_STAGE_HPP_
 #include <hip/hip_runtime.h>
@@ -24,28 +24,6 @@ constexpr int kWave = 64;
 // an empty range is still a valid one
 inline uint32_t blocks_for(uint64_t items) { return (uint32_t)std::max<uint64_t>(1, (items + kThreads - 1) / kThreads); }
 
-// Device memory for the length of one call, allocated through ctx_malloc under
-// a readable name (option "alloc_cap" and the allocation message apply) and
-// freed on return.  p stays null until alloc(): hipcub's size queries take it so.
-template <typename T>
-struct Scratch {
-  T* p = nullptr;
-  Scratch() = default;
-  Scratch(const Scratch&) = delete;
-  Scratch& operator=(const Scratch&) = delete;
-  ~Scratch() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc(mg_ctx* ctx, size_t count, const char* what) {
-    return ctx_malloc(ctx, reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), what);
-  }
-};
-// Scratch::alloc(); returns -1 from the caller with ctx->err set
-#define MG_SCRATCH(buf, count, what)                                      \
-  do {                                                                    \
-    if ((buf).alloc(ctx, (count), (what)) != hipSuccess) return -1;       \
-  } while (0)
-
 // the resident reads
 struct ReadView {
   const uint64_t* words;
@@ -56,7 +34,7 @@ struct ReadView {
 };
 
 inline ReadView view_of(const mg_ctx* ctx) {
-  return ReadView{ctx->d_words, ctx->d_len, ctx->d_phys, ctx->n, ctx->maxw, ctx->stride};
+  return ReadView{ctx->d_words.p, ctx->d_len.p, ctx->d_phys, ctx->n, ctx->maxw, ctx->stride};
 }
 
 // slot of the read with ID idx + 1

@@ -314,31 +314,36 @@ def test_repeatable(engine):
 
 # ---- exchange mode: P simulated ranks in this process, buffers
 # moved by LocalExchange on the device; the same sharded_step drives RCCL ranks
-def exchange_rows(ds, l, world, k=0, want_super=True, opts=None, route_rows=False):
+def exchange_rows(ds, l, world, k=0, want_super=True, opts=None, route_rows=False, opts_after_upload=None):
+    """opts_after_upload: options set on every engine once its reads are resident"""
     import torch
 
     from metagenomics_amd.sharded import LocalExchange, sharded_step, source_range
 
     engines = []
-    for r in range(world):
-        e = OverlapEngine(0)
-        for kk, v in (opts or {}).items():
-            e.set_option(kk, v)
-        e.set_shard(r, world, 0, 0)
-        e.upload(ds)
-        engines.append(e)
-    res = sharded_step(engines, LocalExchange(world, torch.device("cuda:0")), l, k, want_super=want_super,
-                       route_rows=route_rows)
-    exchange_rows.counters = [e.counters() for e in engines]
-    parts = []
-    for r in range(world):
-        rows = res.rows_numpy(r)
-        if route_rows:
-            lo, hi = source_range(ds.num_unique, r, world)
-            assert np.all((rows["src"] >= lo + 1) & (rows["src"] <= hi)), "row at a rank that does not own its src"
-        parts.append(rows)
-    for e in engines:
-        e.close()
+    try:
+        for r in range(world):
+            e = OverlapEngine(0)
+            engines.append(e)
+            for kk, v in (opts or {}).items():
+                e.set_option(kk, v)
+            e.set_shard(r, world, 0, 0)
+            e.upload(ds)
+            for kk, v in (opts_after_upload or {}).items():
+                e.set_option(kk, v)
+        res = sharded_step(engines, LocalExchange(world, torch.device("cuda:0")), l, k, want_super=want_super,
+                           route_rows=route_rows)
+        exchange_rows.counters = [e.counters() for e in engines]
+        parts = []
+        for r in range(world):
+            rows = res.rows_numpy(r)
+            if route_rows:
+                lo, hi = source_range(ds.num_unique, r, world)
+                assert np.all((rows["src"] >= lo + 1) & (rows["src"] <= hi)), "row at a rank that does not own its src"
+            parts.append(rows)
+    finally:
+        for e in engines:
+            e.close()
     return np.concatenate(parts), res.super_read_id
 
 

@@ -9,7 +9,12 @@ and the per-stage structs of mg_ctx.hpp), seen through the calls:
      path of the discovery lists, are swapped with their capacities;
   c. the CSR starts of sorted owners (k_csr_starts) at their edges: no records,
      records of read 1 and of read N, a read without records between two that
-     have some.
+     have some;
+  d. the core context (mg_kernels.hip: upload, index, containment, discovery,
+     rows, lookup, exchange) under the same model: its call-lifetime scratch is
+     named and capped like the stages', and under a ladder of caps every chain
+     either completes with the golden results or fails at a named allocation
+     larger than the cap, and completes on the same engine once the cap is lifted.
 
 Each cap sits one byte below the scratch buffer it names; the buffers the call
 allocates before it are listed with their sizes, restated from the call's code,
@@ -18,6 +23,8 @@ sorts and scans (a few KiB at these sizes) is the one size that is not
 restated; the named buffers are chosen far above it.  Expected results: the
 plain references of ingest_ref.py and mates_ref.py, the golden files, and the
 host mirrors that test_places_host.py and test_mates_host.py pin."""
+import re
+
 import numpy as np
 import pytest
 
@@ -25,11 +32,13 @@ import contigs_ref
 import mates_ref
 import places_ref
 from comp_ref import components_from_rows
-from conftest import golden_rows
+from conftest import fixture_input, golden_rows, load_meta
 from ingest_ref import assert_ingested, pack, ref_dataset
-from metagenomics_amd.overlap import (CONTIG_EDGE_DTYPE, MATE_DTYPE, PLACE_DTYPE, MgError, OverlapEngine,
-                                      host_edge_coverage, host_insert_size_sums, host_mate_pairs, host_placements)
+from metagenomics_amd.overlap import (CONTIG_EDGE_DTYPE, MATE_DTYPE, PLACE_DTYPE, Dataset, MgError, OverlapEngine,
+                                      host_edge_coverage, host_insert_size_sums, host_mate_pairs, host_placements,
+                                      rows_to_tuples)
 from test_discoveries import assert_lists, expected
+from test_gpu_parity import exchange_rows
 from test_places import boundary_case, engine_for, mate_csr
 
 pytestmark = pytest.mark.gpu
@@ -312,3 +321,106 @@ def test_placement_starts(lists, owners):
         assert np.array_equal(start, hs) and np.array_equal(recs, hr)
     finally:
         eng.close()
+
+
+# ---- d. the core context's buffers
+
+def core_fixture(name):
+    """(meta, Dataset, the h-base key at the start of read 1) of a golden fixture"""
+    meta = load_meta(name)
+    ds = Dataset.from_files([fixture_input(name)], meta["l"])
+    return meta, ds, ds.read(1)[: meta["l"] - 1]
+
+
+def super_of(sup):
+    return {str(i): int(s) for i, s in enumerate(sup) if s}
+
+
+def test_lookup_names_its_scratch():
+    meta, ds, key = core_fixture("small")
+    before = {"lookup key": ((len(key) + 31) // 32 + 1) * 8}
+    target = 1024 * 8  # "lookup results": the binding's first buffer of 1,024 entries
+    assert max(before.values()) < target
+    eng = OverlapEngine(0)
+    try:
+        eng.set_option("nb_log2", 10)
+        eng.upload(ds)
+        eng.build_index(meta["l"])
+        want = eng.lookup(key)  # (the first lookup after a build files the lookup table, far above the cap)
+        assert (1, 0) in want
+        assert expect_named_failure(eng, target - 1, "lookup results", lambda: eng.lookup(key)) == want
+    finally:
+        eng.close()
+
+
+def test_upload_ascii_names_its_scratch():
+    meta, ds, _ = core_fixture("small")
+    seqs = [ds.read(i) for i in range(1, ds.num_unique + 1)]
+    total = sum(map(len, seqs))  # "upload records": the call's first allocation on a fresh context
+    eng = OverlapEngine(0)
+    try:
+        expect_named_failure(eng, total - 1, "upload records", lambda: eng.upload_ascii(seqs))
+        eng.build_index(meta["l"])
+        eng.mark_contained()
+        assert np.array_equal(rows_to_tuples(eng.rows()), golden_rows("small"))
+    finally:
+        eng.close()
+
+
+LADDER = [1 << s for s in (8, 12, 16, 20, 24)]
+ALLOC_FAILURE = re.compile(r"device allocation of (.+) \((\d+) B\) failed: ")
+
+
+def assert_capped(err, cap):
+    """the failure names a buffer larger than the cap and the option that refused it"""
+    msg = str(err)
+    print(cap, msg)
+    m = ALLOC_FAILURE.search(msg)
+    assert m and "alloc_cap" in msg, msg
+    assert int(m.group(2)) > cap, msg
+
+
+@pytest.mark.parametrize("name", ["small", "mixed"])
+def test_core_allocation_ladder(name):
+    meta, ds, key = core_fixture(name)
+    want_rows = golden_rows(name)
+
+    def chain(eng):
+        eng.upload(ds)
+        eng.build_index(meta["l"])
+        sup = eng.mark_contained()
+        rows = eng.rows(eng.find_overlaps())
+        assert (1, 0) in eng.lookup(key)
+        assert np.array_equal(rows_to_tuples(rows), want_rows) and super_of(sup) == meta["super"]
+
+    failed = []
+    for cap in LADDER:
+        eng = OverlapEngine(0)
+        try:
+            eng.set_option("alloc_cap", cap)
+            try:
+                chain(eng)
+            except MgError as e:
+                assert_capped(e, cap)
+                failed.append(cap)
+            eng.set_option("alloc_cap", 0)
+            chain(eng)
+        finally:
+            eng.close()
+    assert failed and len(failed) < len(LADDER), failed  # some cap refuses an allocation, some cap lets the chain through
+
+
+def test_exchange_allocation_ladder():
+    """the same ladder through the exchange step of two ranks, the caps set once the reads are resident"""
+    meta, ds, _ = core_fixture("small")
+    want_rows = golden_rows("small")
+    failed = []
+    for cap in LADDER:
+        try:
+            rows, sup = exchange_rows(ds, meta["l"], 2, opts_after_upload={"alloc_cap": cap})
+        except MgError as e:
+            assert_capped(e, cap)
+            failed.append(cap)
+        else:
+            assert np.array_equal(rows_to_tuples(rows), want_rows) and super_of(sup) == meta["super"]
+    assert failed and len(failed) < len(LADDER), failed
