@@ -291,6 +291,13 @@ class OverlapGraph {
   // always the serial replay.  The same graph either way.  Until this is
   // called the environment variable MG_DEVICE_COMP decides (0 = serial).
   static void setDeviceComponents(bool on);
+  // The contraction loop that ends buildOverlapGraphFromHashTable: the safe
+  // chains of the replayed graph are found on the device (mg_build_chains, list
+  // ranking) and contracted first, then the loop runs unchanged; the same
+  // graph, lists, locations and counters.  Off: the loop alone.
+  // Until this is called the environment variable MG_DEVICE_CHAINS decides
+  // (0 = off).  The caller-driven contractCompositePaths() is not affected.
+  static void setDeviceChains(bool on);
   // the contraction loop's steps (:669-696, :931-988) on the current graph
   // (available once the graph was built with replayExploration)
   UINT64 contractCompositePaths();

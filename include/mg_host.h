@@ -186,6 +186,44 @@ uint64_t mgh_graph_rows(const mgh_graph* g, mg_edge* out, uint64_t cap);
  * -4 an orientation pair mergedEdgeOrientation rejects (:830-833 MYEXIT). */
 int mgh_graph_contract(mgh_graph* g, int track_locations, uint64_t* iterations, uint64_t* merged,
                        uint64_t* dead_end_nodes);
+/* --- safe chains: the order-free bulk of the first contraction pass ------------
+ * Definitions: include/mg_overlap.h ("safe chains"); argument: DESIGN.md §7d.
+ * The replayed (not yet contracted) graph as the CSR mg_build_chains and
+ * mgh_chains_build take: u order, each list in list order (the order of
+ * mgh_graph_rows), twin = CSR index of the reverse edge.  start: n_reads + 2
+ * entries; edges: cap records; either may be NULL.  Returns the number of
+ * half-edges (0 for a contracted handle); beyond cap nothing is written. */
+uint64_t mgh_graph_simple_csr(const mgh_graph* g, uint64_t* start, mg_chain_edge* edges, uint64_t cap);
+/* The inverse: an uncontracted handle whose lists are those of the CSR (edges
+ * created in CSR order), for graphs that no discovery multiset produced (tests,
+ * the stand-alone check).  0 = ok; -1 = bad arguments; -2 = a malformed CSR, as
+ * mg_build_chains refuses it. */
+int mgh_graph_from_csr(const uint64_t* start, const mg_chain_edge* edges, uint64_t n_reads, uint64_t n_edges,
+                       mgh_graph** out);
+/* The host mirror of mg_build_chains + mg_copy_chains (mg::chains_build): a
+ * serial walk over the same CSR, the definition of the device's arrays, in the
+ * same order.  rounds: as option "chain_rounds" (0 = auto).  chains: chain_cap
+ * records; reads / offs / ors: list_cap entries; written only when the cap
+ * holds all of them.  info: MG_CHAIN_INFO counters.  Any output may be NULL.
+ * 0 = ok; -1 = bad arguments; -2 = as mg_build_chains (err names the entry). */
+int mgh_chains_build(const uint64_t* start, const mg_chain_edge* edges, uint64_t n_reads, uint64_t n_edges,
+                     uint32_t rounds, mg_chain* chains, uint64_t chain_cap, uint32_t* reads, uint16_t* offs,
+                     uint8_t* ors, uint64_t list_cap, uint64_t* n_chains, uint64_t* n_list, uint64_t* info, char* err,
+                     uint64_t err_cap);
+/* mgh_graph_contract with a table of safe chains of this handle's CSR
+ * contracted first (mg::UnitigGraph::apply_chains): the edges a -> b and b -> a
+ * of every chain installed at lists[a][pa] and lists[b][pb], the interior lists
+ * emptied, read locations added, then the loop unchanged, with the contracted
+ * nodes counted as merges of its first pass.  The handle ends in the state
+ * mgh_graph_contract leaves: lists in list order, read lists, location lists in
+ * list order, counters, *iterations, *merged, *dead_end_nodes.  Any subset of
+ * the safe chains may be given.  The table is validated for soundness (every
+ * entry locally, threaded; ends; no read in two chains; each chain's safeness
+ * from a's list): -4 = it is not a set of safe chains of this graph, and the
+ * handle is unchanged (still uncontracted).  Other codes as mgh_graph_contract. */
+int mgh_graph_contract_chains(mgh_graph* g, const mg_chain* chains, uint64_t n_chains, const uint32_t* reads,
+                              const uint16_t* offs, const uint8_t* ors, uint64_t n_list, int track_locations,
+                              uint64_t* iterations, uint64_t* merged, uint64_t* dead_end_nodes);
 /* sortEdges (:2799-2808): every list sorted by destination ID (std::sort). */
 int mgh_graph_sort_edges(mgh_graph* g);
 /* saveGraphToFile (:1219-1261): the .unitig checkpoint of the current graph

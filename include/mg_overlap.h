@@ -221,6 +221,74 @@ int mg_build_components(mg_ctx* ctx, uint64_t* n_comp, float* device_ms);
  * invalidates the lists, and every mg_build_discoveries, invalidates it. */
 int mg_copy_components(mg_ctx* ctx, uint32_t* label, mg_comp* comps, uint64_t cap, uint64_t* n_copied);
 
+/* --- safe chains of the replayed graph ("Safe chains") ----------
+ * The first contractCompositePaths pass (OverlapGraph.cpp:669-696) of a freshly
+ * replayed graph (every edge simple, no flow) is order-free on most of the
+ * graph.  Input: the graph as a CSR in u order, each list in list order
+ * (mgh_graph_simple_csr, include/mg_host.h): list of read u =
+ * edges[start[u] .. start[u + 1]), start has n_reads + 2 entries with
+ * start[0] = start[1] = 0 and start[n_reads + 1] = n_edges < 2^32. */
+typedef struct mg_chain_edge { /* 12 bytes: one half-edge */
+  uint32_t dst;                /* read ID of its far node */
+  uint32_t twin;               /* CSR index of its reverse edge (in dst's list) */
+  uint16_t offset;             /* overlapOffset */
+  uint8_t orient;              /* overlapOrientation */
+  uint8_t pad;
+} mg_chain_edge;
+/* A node is INTERIOR when its list is [e0, e1], matchEdgeType(twin(e0), e1)
+ * holds and e0 is no self-loop: the nodes contractCompositePaths may merge at.
+ * A CHAIN is a maximal path a -> n1 -> .. -> nk -> b of interior nodes between
+ * two half-edges (a, pa), (b, pb) of non-interior nodes (pa = position in a's
+ * list).  The FAR END of a half-edge of a non-interior node is its dst when that
+ * is non-interior, else the other end of the chain it heads.  A chain is SAFE
+ * when a < b and no other half-edge of a's list has far end b (nor an unknown
+ * one, see "chain_rounds"): isEdgePresent (:679) is then false at each of its
+ * nodes in any order, and contracting it first leaves the loop's result
+ * unchanged.  One safe chain, its n interior nodes contracted into the edge
+ * a -> b and its reverse (mergeEdges / mergeList, :702-785): */
+typedef struct mg_chain { /* 48 bytes */
+  uint32_t a, b;          /* end nodes, a < b */
+  uint32_t pa, pb;        /* positions of the end half-edges in a's and b's list */
+  uint32_t n;             /* interior nodes */
+  uint8_t orient_fwd;     /* orientation of a -> b */
+  uint8_t orient_rev;     /* orientation of b -> a */
+  uint8_t pad[2];
+  uint64_t offset_fwd;    /* overlapOffset of a -> b: the sum over its n + 1 edges */
+  uint64_t offset_rev;    /* the same for b -> a */
+  uint64_t first;         /* its lists: forward [first, first + n), reverse [first + n, first + 2 n) */
+} mg_chain;
+/* counters of a build (mg_build_chains, mgh_chains_build) */
+enum { MG_CHAIN_INTERIOR = 0,   /* interior nodes */
+       MG_CHAIN_SAFE = 1,       /* safe chains (the table's length) */
+       MG_CHAIN_CONTRACTED = 2, /* interior nodes on them */
+       MG_CHAIN_UNSAFE = 3,     /* chains with both ends known that are not safe */
+       MG_CHAIN_UNRESOLVED = 4, /* (node, port) states without a known end: pure cycles, chains over the cap */
+       MG_CHAIN_ROUNDS = 5,     /* pointer-jumping rounds run */
+       MG_CHAIN_INFO = 6 };
+/* The safe chains on the device, in ascending start[a] + pa: list ranking by
+ * pointer jumping over the 2 n_interior (node, port) states, two scans and a
+ * scatter of the read lists (reads / listOfOverlapOffsets / listOfOrientations
+ * of both new edges).  Needs a context only: no reads, no index.  A function of
+ * the CSR alone: two calls give identical arrays, equal to mgh_chains_build's.
+ * At most ceil(log2(n_interior + 1)) + 1 rounds run (every chain's ends are
+ * known by then), fewer when a round finds no new end; option "chain_rounds"
+ * lowers that cap: a chain is then known only when it has at most 2^rounds
+ * interior nodes, and a half-edge that heads an unknown chain makes every chain
+ * of its node unsafe.  *n_chains, *n_list = lengths of the table and of the
+ * lists; info (optional) = MG_CHAIN_INFO counters; *device_ms (optional) =
+ * HIP-event time from the first kernel to the last.  -1 = bad arguments, a
+ * sharded / exchange-mode context, a device error; -2 = start not monotone
+ * from 0 to n_edges, a dst outside 1..n_reads, a twin outside its dst's list,
+ * twin[twin[e]] != e or a twin whose dst is not e's node: mg_last_error names
+ * the first such entry, found before anything is indexed through it. */
+int mg_build_chains(mg_ctx* ctx, const uint64_t* start, const mg_chain_edge* edges, uint64_t n_reads,
+                    uint64_t n_edges, uint64_t* n_chains, uint64_t* n_list, uint64_t* info, float* device_ms);
+/* chains: chain_cap records; reads / offs / ors: list_cap entries each.  Any may
+ * be NULL; what exceeds a cap is not written.  Fails unless mg_build_chains
+ * succeeded on this context. */
+int mg_copy_chains(mg_ctx* ctx, mg_chain* chains, uint64_t chain_cap, uint32_t* reads, uint16_t* offs, uint8_t* ors,
+                   uint64_t list_cap);
+
 /* --- read lookup and mate pairs (Dataset::getReadFromString, storeMatePairInformation)
  * Batched Dataset::getReadFromString (Dataset.cpp:421-455) over the resident
  * reads.  Raw record i = concat[offsets[i], offsets[i+1]), any case, as
@@ -709,6 +777,8 @@ int mg_get_counters(const mg_ctx* ctx, mg_counters* c);
  *  "path_budget"    work units one mate entry of mg_mate_paths may spend before it is
  *                   deferred to the host mirror (0 = default 2^16): the one option a
  *                   call's own output depends on; the finished result does not;
+ *  "chain_rounds"   tests: cap on the pointer-jumping rounds of mg_build_chains (0 = auto);
+ *                   chains of more than 2^rounds interior nodes are then left out;
  *  "phase_limit", "max_blocks"
  *                   diagnostics: stop the probe after a phase / cap its grid. */
 int mg_set_option(mg_ctx* ctx, const char* name, int64_t value);

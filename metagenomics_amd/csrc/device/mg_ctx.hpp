@@ -4,8 +4,9 @@
 // per-read discovery lists D(A); mg_comp.hip: their components; mg_mates.hip:
 // read lookup and the per-read mate lists; mg_contigs.hip: the strings of edges;
 // mg_places.hip: read placements, insert sizes and edge coverage; mg_paths.hip:
-// mate-pair paths).  The core fields of mg_ctx belong to mg_kernels.hip; each
-// derived stage keeps its state in one struct (DiscStage .. PathStage: ready
+// mate-pair paths; mg_chains.hip: safe chains of a replayed graph).  The core
+// fields of mg_ctx belong to mg_kernels.hip; each
+// derived stage keeps its state in one struct (DiscStage .. ChainStage: ready
 // flag, counts, test options, buffers, EventPair) that mg_ctx embeds by value.
 // The whole context follows one ownership model: every resident device buffer
 // is a DevArray (grown with MG_GROW / MG_ENSURE, freed by its destructor when
@@ -210,6 +211,40 @@ struct PathStage {
   // "path_budget" (work units per mate entry, 0 = 2^16)
   uint64_t batch = 0, budget = 0;
   float explore_ms = 0.f, aggregate_ms = 0.f;
+  EventPair ev;
+};
+
+// one (node, port) state of the chain ranking (mg_chains.hip): "leaving node v
+// through port p".  Unknown end: link = the next state.  Known end: link = the
+// CSR index of the end half-edge, end = its node.  out / in = sums of the
+// offsets of the edges walked and of their twins.
+struct ChainState {
+  uint32_t link;
+  uint32_t hops;  // edges walked; bit 31 = the end is known; 0 = no state (the node is not interior)
+  uint32_t end;
+  uint32_t pad;
+  uint64_t out, in;
+};
+
+// safe chains of a replayed graph (mg_chains.hip, mg_build_chains): the table
+// and the SoA read lists of the last build; ready until the next build
+struct ChainStage {
+  bool ready = false;
+  uint64_t n_chains = 0, n_list = 0;
+  uint32_t rounds = 0;  // option "chain_rounds" (tests): cap on the jump rounds (0 = auto)
+  DevArray<uint64_t> start;        // the caller's CSR starts (n + 2)
+  DevArray<mg_chain_edge> edges;   // and half-edges
+  DevArray<uint8_t> interior;      // per node (n + 2)
+  DevArray<ChainState> state[2];   // 2 (n + 1) states, double-buffered over the rounds
+  DevArray<uint32_t> far_end;      // per half-edge of a non-interior node: its far end, 0 = unknown
+  DevArray<uint32_t> head;         // per half-edge: 1 = heads a safe chain; then its chain index (scan)
+  DevArray<uint64_t> span;         // per half-edge: 2 n of the safe chain it heads; then its `first` (scan)
+  DevArray<uint8_t> tmp;           // the scans' temporary storage
+  DevArray<unsigned long long> ctl;  // control words (see mg_chains.hip)
+  DevArray<mg_chain> table;
+  DevArray<uint32_t> reads;
+  DevArray<uint16_t> offs;
+  DevArray<uint8_t> ors;
   EventPair ev;
 };
 
@@ -487,6 +522,7 @@ struct mg_ctx {
   ContigStage contigs;
   PlaceStage places;
   PathStage paths;
+  ChainStage chains;
 };
 
 #define MG_TRY(expr)                                                                  \

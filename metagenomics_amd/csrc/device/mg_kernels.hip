@@ -4353,6 +4353,10 @@ int mg_set_option(mg_ctx* ctx, const char* name, int64_t value) {
     ctx->paths.budget = (uint64_t)std::max<int64_t>(0, value);
     return 0;
   }
+  if (!strcmp(name, "chain_rounds")) {  // tests: cap on the jump rounds of mg_build_chains (0 = auto)
+    ctx->chains.rounds = (uint32_t)std::max<int64_t>(0, std::min<int64_t>(value, 64));
+    return 0;
+  }
   if (!strcmp(name, "run_cap")) {  // tests: initial run records per scan region (0 = sized from the reads)
     ctx->run_cap_opt = (uint64_t)std::max<int64_t>(0, value);
     ctx->run_cap_need = 0;

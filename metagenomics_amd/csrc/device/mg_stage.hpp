@@ -1,6 +1,6 @@
 // mg_stage.hpp — INTERNAL: what the derived-stage translation units share
 // beyond the context (mg_dataset.hip, mg_disc.hip, mg_comp.hip, mg_mates.hip,
-// mg_contigs.hip, mg_places.hip): the view of the resident reads, the launch
+// mg_contigs.hip, mg_places.hip, mg_chains.hip): the view of the resident reads, the launch
 // grid, the CSR starts of sorted owners, control words, the copy tail of the
 // mg_copy_* calls and the edge lists that mg_build_contigs and
 // mg_build_placements both take.  (DevArray, Scratch and their growth macros

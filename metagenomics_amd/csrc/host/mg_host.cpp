@@ -17,6 +17,7 @@
 #include <unordered_map>
 
 #include "mg_api.hpp"
+#include "mg_chains.hpp"
 #include "mg_contigs.hpp"
 #include "mg_mates.hpp"
 #include "mg_parse.hpp"
@@ -1185,8 +1186,40 @@ void mate_pairs_on(Dataset* ds, mg_ctx** slot, mg_ctx* ctx) {
 }
 }  // namespace
 
+namespace {
+// The safe chains of the replayed graph found on the device and contracted
+// before the loop runs (mg_build_chains, UnitigGraph::apply_chains; DESIGN.md
+// §7d).  g_device_chains: OverlapGraph::setDeviceChains; -1 = not called, the
+// environment variable MG_DEVICE_CHAINS decides (unset: on; 0 = the loop alone)
+int g_device_chains = -1;
+
+bool env_device_chains() {
+  const char* v = std::getenv("MG_DEVICE_CHAINS");
+  return v && *v ? std::atoi(v) != 0 : true;
+}
+
+// returns the nodes contracted: the first pass's credit
+uint64_t contract_device_chains(mg_ctx* ctx, const mg::GraphReplay& rp, mg::UnitigGraph* u) {
+  std::vector<uint64_t> start;
+  std::vector<mg_chain_edge> edges;
+  mg::simple_csr(rp.pool, rp.lists, &start, &edges);
+  uint64_t nc = 0, nl = 0, credit = 0;
+  if (mg_build_chains(ctx, start.data(), edges.data(), start.size() - 2, edges.size(), &nc, &nl, nullptr, nullptr))
+    mg::fail(ctx, "build chains");
+  std::vector<mg_chain> table(nc);
+  std::vector<uint32_t> reads(nl);
+  std::vector<uint16_t> offs(nl);
+  std::vector<uint8_t> ors(nl);
+  if (mg_copy_chains(ctx, table.data(), nc, reads.data(), offs.data(), ors.data(), nl)) mg::fail(ctx, "copy chains");
+  if (u->apply_chains(table.data(), nc, reads.data(), offs.data(), ors.data(), nl, mg::replay_threads(), &credit))
+    throw mg::Error("chains inconsistent with the replayed graph (-4)");
+  return credit;
+}
+}  // namespace
+
 void OverlapGraph::setDeviceDiscoveries(bool on) { g_device_disc = on ? 1 : 0; }
 void OverlapGraph::setDeviceComponents(bool on) { g_device_comp = on ? 1 : 0; }
+void OverlapGraph::setDeviceChains(bool on) { g_device_chains = on ? 1 : 0; }
 
 bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
   // OverlapGraph.cpp:107-218 up to the end of edge discovery: containment,
@@ -1239,7 +1272,11 @@ bool OverlapGraph::buildOverlapGraphFromHashTable(HashTable* ht) {
     if (rc) throw mg::Error("components inconsistent with the discovery lists (" + std::to_string(rc) + ")");
     unitig = new mg::UnitigGraph();
     unitig->init(rp, N, true);
-    if (contractPaths && unitig->contract() < 0) throw mg::Error("Unable to merge.");  // :211-215
+    if (contractPaths) {  // :211-215
+      const bool chains = g_device_chains < 0 ? env_device_chains() : g_device_chains != 0;
+      const uint64_t credit = chains ? contract_device_chains(ctx, rp, unitig) : 0;
+      if (unitig->contract(credit) < 0) throw mg::Error("Unable to merge.");
+    }
     materialize();
   }
   delete ht;  // the graph owns and frees the table (:210)
@@ -1701,6 +1738,102 @@ int mgh_graph_contract(mgh_graph* g, int track_locations, uint64_t* iterations, 
     if (dead_end_nodes) *dead_end_nodes = u->dead_end_total;
     g->u = std::move(u);
     // the pre-contraction graph is no longer needed
+    std::vector<mg::GraphEdge>().swap(g->g.pool);
+    std::vector<std::vector<uint32_t>>().swap(g->g.lists);
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+uint64_t mgh_graph_simple_csr(const mgh_graph* g, uint64_t* start, mg_chain_edge* edges, uint64_t cap) {
+  if (!g || g->u) return 0;
+  try {
+    std::vector<uint64_t> s;
+    std::vector<mg_chain_edge> e;
+    mg::simple_csr(g->g.pool, g->g.lists, &s, &e);
+    if (start) std::copy(s.begin(), s.end(), start);
+    if (edges && cap >= e.size()) std::copy(e.begin(), e.end(), edges);
+    return e.size();
+  } catch (const std::exception&) {
+    return 0;
+  }
+}
+
+int mgh_graph_from_csr(const uint64_t* start, const mg_chain_edge* edges, uint64_t n_reads, uint64_t n_edges,
+                       mgh_graph** out) {
+  if (!out || !start || (n_edges && !edges)) return -1;
+  *out = nullptr;
+  try {
+    if (mg::chains_check_csr(start, edges, n_reads, n_edges, nullptr)) return -2;
+    std::unique_ptr<mgh_graph> g(new mgh_graph());
+    g->g.pool.resize(n_edges);
+    g->g.lists.assign(n_reads + 1, {});
+    for (uint64_t u = 1; u <= n_reads; ++u) {
+      for (uint64_t e = start[u]; e < start[u + 1]; ++e) {
+        g->g.pool[e] = mg::GraphEdge{(uint32_t)u, edges[e].dst, edges[e].offset, edges[e].orient, 0, edges[e].twin};
+        g->g.lists[u].push_back((uint32_t)e);
+      }
+      g->g.nodes += start[u + 1] > start[u];
+    }
+    g->g.edges = n_edges;
+    *out = g.release();
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_chains_build(const uint64_t* start, const mg_chain_edge* edges, uint64_t n_reads, uint64_t n_edges,
+                     uint32_t rounds, mg_chain* chains, uint64_t chain_cap, uint32_t* reads, uint16_t* offs,
+                     uint8_t* ors, uint64_t list_cap, uint64_t* n_chains, uint64_t* n_list, uint64_t* info, char* err,
+                     uint64_t err_cap) {
+  if (n_chains) *n_chains = 0;
+  if (n_list) *n_list = 0;
+  if (err && err_cap) err[0] = 0;
+  if (!start || (n_edges && !edges)) return -1;
+  try {
+    mg::ChainTable t;
+    std::string e;
+    const int rc = mg::chains_build(start, edges, n_reads, n_edges, rounds, &t, &e);
+    if (rc) {
+      if (err && err_cap) {
+        const size_t n = std::min<size_t>(e.size(), err_cap - 1);
+        std::memcpy(err, e.data(), n);
+        err[n] = 0;
+      }
+      return rc;
+    }
+    if (chains && chain_cap >= t.chains.size()) std::copy(t.chains.begin(), t.chains.end(), chains);
+    if (list_cap >= t.reads.size()) {
+      if (reads) std::copy(t.reads.begin(), t.reads.end(), reads);
+      if (offs) std::copy(t.offs.begin(), t.offs.end(), offs);
+      if (ors) std::copy(t.ors.begin(), t.ors.end(), ors);
+    }
+    if (n_chains) *n_chains = t.chains.size();
+    if (n_list) *n_list = t.reads.size();
+    if (info) std::copy(t.info, t.info + MG_CHAIN_INFO, info);
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_graph_contract_chains(mgh_graph* g, const mg_chain* chains, uint64_t n_chains, const uint32_t* reads,
+                              const uint16_t* offs, const uint8_t* ors, uint64_t n_list, int track_locations,
+                              uint64_t* iterations, uint64_t* merged, uint64_t* dead_end_nodes) {
+  if (!g || g->u) return -1;
+  try {
+    auto u = std::make_unique<mg::UnitigGraph>();
+    u->init(g->g, g->g.lists.empty() ? 0 : g->g.lists.size() - 1, track_locations != 0);
+    uint64_t credit = 0;
+    if (u->apply_chains(chains, n_chains, reads, offs, ors, n_list, mg::replay_threads(), &credit)) return -4;
+    const int64_t it = u->contract(credit);
+    if (it < 0) return -4;
+    if (iterations) *iterations = (uint64_t)it;
+    if (merged) *merged = u->merged_total;
+    if (dead_end_nodes) *dead_end_nodes = u->dead_end_total;
+    g->u = std::move(u);
     std::vector<mg::GraphEdge>().swap(g->g.pool);
     std::vector<std::vector<uint32_t>>().swap(g->g.lists);
   } catch (const std::exception&) {

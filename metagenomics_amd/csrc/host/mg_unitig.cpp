@@ -405,11 +405,12 @@ uint64_t UnitigGraph::remove_dead_end_nodes() {  // :931-988
   return nodes_out.size();
 }
 
-int64_t UnitigGraph::contract() {
+int64_t UnitigGraph::contract(uint64_t first_pass_credit) {
   int64_t iters = 0;
   uint64_t counter = 0;
+  merged_total += first_pass_credit;
   do {
-    counter = contract_composite_paths();
+    counter = contract_composite_paths() + (iters ? 0 : first_pass_credit);
     if (bad_merge) return -1;
     counter += remove_dead_end_nodes();
     iters++;

@@ -48,7 +48,21 @@ class UnitigGraph {
   // do { contractCompositePaths(); removeDeadEndNodes(); } while (changed)
   // (:211-215).  Returns the number of loop iterations; < 0 on an
   // orientation the reference would MYEXIT on ("Unable to merge.").
-  int64_t contract();
+  // first_pass_credit: nodes apply_chains contracted, counted as merges of the
+  // first contractCompositePaths pass (merged_total and the loop's test)
+  int64_t contract(uint64_t first_pass_credit = 0);
+  // Contracts a table of safe chains of the freshly initialised graph (every
+  // edge simple, no flow; mg_chain and the lists as mg_build_chains /
+  // chains_build give them) before contract() runs: installs a -> b at
+  // lists[a][pa] and b -> a at lists[b][pb] (forward edge created first), empties
+  // the interior lists, adds the read locations and adjusts nodes / edges.  The
+  // table is validated first (mg_chains.cpp): every entry an interior node linked
+  // to its neighbours through twin pairs with that twin's offset and orientation,
+  // ends non-interior with a < b, no read twice, the records' sums and
+  // orientations, and each chain safe from a's list.  0 = ok (*contracted =
+  // interior nodes contracted); -4 = the table is not sound, nothing changed.
+  int apply_chains(const mg_chain* chains, uint64_t n_chains, const uint32_t* reads, const uint16_t* offs,
+                   const uint8_t* ors, uint64_t n_list, unsigned threads, uint64_t* contracted);
   uint64_t contract_composite_paths();  // :669-696
   uint64_t remove_dead_end_nodes();     // :931-988
   void sort_edges();                    // :2799-2808

@@ -42,6 +42,29 @@ PAIR_DTYPE = np.dtype([("edge1", "<u4"), ("edge2", "<u4"), ("support", "<u8")])
 PATH_SKIPPED, PATH_SAME_EDGE, PATH_NONE, PATH_FOUND, PATH_DEFERRED = range(5)
 # the reference's minimumSupport (Common.h:43)
 MIN_SUPPORT = 3
+# one half-edge of a replayed graph's CSR (mg_chain_edge, include/mg_overlap.h): 12 bytes
+CHAIN_EDGE_DTYPE = np.dtype([("dst", "<u4"), ("twin", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("pad", "u1")])
+# one safe chain (mg_chain, include/mg_overlap.h): 48 bytes
+CHAIN_DTYPE = np.dtype({"names": ["a", "b", "pa", "pb", "n", "orient_fwd", "orient_rev", "offset_fwd", "offset_rev",
+                                  "first"],
+                        "formats": ["<u4", "<u4", "<u4", "<u4", "<u4", "u1", "u1", "<u8", "<u8", "<u8"],
+                        "offsets": [0, 4, 8, 12, 16, 20, 21, 24, 32, 40], "itemsize": 48})
+# the counters of a chain build (MG_CHAIN_*, include/mg_overlap.h)
+CHAIN_INFO = ("n_interior", "n_chains", "n_contracted", "n_unsafe_chains", "n_unresolved_states", "rounds")
+
+
+class Chains:
+    """The safe chains of a replayed graph (OverlapEngine.chains / host_chains):
+    chains[CHAIN_DTYPE] in ascending start[a] + pa, the SoA read lists of their
+    edges (forward [first, first + n), reverse [first + n, first + 2 n)) and the
+    build's counters (info, keys CHAIN_INFO)."""
+
+    def __init__(self, chains, reads, offs, ors, info):
+        self.chains, self.reads, self.offs, self.ors = chains, reads, offs, ors
+        self.info = dict(zip(CHAIN_INFO, (int(v) for v in info)))
+
+    def arrays(self):
+        return self.chains, self.reads, self.offs, self.ors
 
 
 class MgError(RuntimeError):
@@ -189,6 +212,13 @@ def lib() -> C.CDLL:
         "mgh_mate_paths": (i32, [u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                  vp, u64, P(u64), vp, u64, P(u64), vp, C.c_char_p, u64]),
         "mgh_graph_merge_supported": (i32, [vp, vp, u64, u64, P(u64), C.c_char_p, u64]),
+        "mg_build_chains": (i32, [vp, vp, vp, u64, u64, P(u64), P(u64), vp, P(C.c_float)]),
+        "mg_copy_chains": (i32, [vp, vp, u64, vp, vp, vp, u64]),
+        "mgh_graph_simple_csr": (u64, [vp, vp, vp, u64]),
+        "mgh_graph_from_csr": (i32, [vp, vp, u64, u64, P(vp)]),
+        "mgh_chains_build": (i32, [vp, vp, u64, u64, u32, vp, u64, vp, vp, vp, u64, P(u64), P(u64), vp, C.c_char_p,
+                                   u64]),
+        "mgh_graph_contract_chains": (i32, [vp, vp, u64, vp, vp, vp, u64, i32, P(u64), P(u64), P(u64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)
@@ -720,6 +750,33 @@ class OverlapEngine:
         self._check(lib().mg_copy_components(self._h, _ptr(label), _ptr(comps), n, C.byref(got)), "copy_components")
         return label, comps[: got.value]
 
+    # --- safe chains of a replayed graph, ranked on the device
+    def build_chains(self, start: np.ndarray, edges: np.ndarray) -> int:
+        """mg_build_chains on a replayed graph's CSR (simple_csr): finds the safe
+        chains by list ranking and emits the read lists of their edges, on the
+        device.  Needs no reads and no index.  Returns the number of chains;
+        chains_ms keeps the device time, chain_info the counters (CHAIN_INFO)."""
+        start, edges = _chain_csr(start, edges)
+        self._chain_csr = (start, edges)  # (the arrays outlive the call)
+        n, nl, ms = C.c_uint64(), C.c_uint64(), C.c_float()
+        info = np.zeros(len(CHAIN_INFO), dtype=np.uint64)
+        self._n_chains = None
+        rc = lib().mg_build_chains(self._h, _ptr(start), _ptr(edges), start.shape[0] - 2, edges.shape[0], C.byref(n),
+                                   C.byref(nl), _ptr(info), C.byref(ms))
+        self._check(rc, "build_chains")
+        self.chains_ms = float(ms.value)
+        self.chain_info = dict(zip(CHAIN_INFO, (int(v) for v in info)))
+        self._n_chains = (int(n.value), int(nl.value))
+        return int(n.value)
+
+    def chains(self) -> "Chains":
+        """mg_copy_chains: the table and lists of the last build_chains."""
+        n, nl = getattr(self, "_n_chains", None) or (0, 0)
+        ch = np.zeros(n, dtype=CHAIN_DTYPE)
+        reads, offs, ors = np.zeros(nl, dtype=np.uint32), np.zeros(nl, dtype=np.uint16), np.zeros(nl, dtype=np.uint8)
+        self._check(lib().mg_copy_chains(self._h, _ptr(ch), n, _ptr(reads), _ptr(offs), _ptr(ors), nl), "copy_chains")
+        return Chains(ch, reads, offs, ors, [self.chain_info[k] for k in CHAIN_INFO])
+
     def lookup(self, key: str):
         n = C.c_uint64()
         cap = 1024
@@ -864,6 +921,67 @@ def _replay_disc(start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_over
     if rc:
         raise MgError(f"graph replay failed ({rc})")
     return g
+
+
+def _chain_csr(start, edges):
+    start = np.ascontiguousarray(start, dtype=np.uint64)
+    edges = np.ascontiguousarray(edges, dtype=CHAIN_EDGE_DTYPE)
+    if start.shape[0] < 2:
+        raise MgError("chain CSR: start must have n_reads + 2 entries")
+    return start, edges
+
+
+def simple_csr(rows: np.ndarray, lens: np.ndarray, min_overlap: int):
+    """(start uint64[n_reads + 2], edges[CHAIN_EDGE_DTYPE]) of the replayed graph
+    of a discovery multiset (mgh_graph_replay + mgh_graph_simple_csr): u order,
+    each list in list order, twin = CSR index of the reverse edge: the input
+    of OverlapEngine.build_chains and host_chains."""
+    rows = np.ascontiguousarray(rows, dtype=EDGE_DTYPE)
+    lens = np.ascontiguousarray(lens, dtype=np.uint16)
+    L = lib()
+    g = C.c_void_p()
+    rc = L.mgh_graph_replay(_ptr(rows), rows.shape[0], _ptr(lens), lens.shape[0], min_overlap - 1, C.byref(g))
+    if rc:
+        raise MgError(f"graph replay failed ({rc})")
+    try:
+        return _graph_csr(g, lens.shape[0])
+    finally:
+        L.mgh_graph_free(g)
+
+
+def _graph_csr(g, n_reads: int):
+    L = lib()
+    n = int(L.mgh_graph_simple_csr(g, None, None, 0))
+    start = np.zeros(n_reads + 2, dtype=np.uint64)
+    edges = np.zeros(n, dtype=CHAIN_EDGE_DTYPE)
+    L.mgh_graph_simple_csr(g, _ptr(start), _ptr(edges), n)
+    return start, edges
+
+
+def host_chains(start: np.ndarray, edges: np.ndarray, rounds: int = 0) -> Chains:
+    """The safe chains from the host's serial walk (mgh_chains_build,
+    mg::chains_build): what OverlapEngine.chains gives, in the same order;
+    rounds as the engine's option chain_rounds.  MgError (-2) names the first
+    malformed entry of the CSR."""
+    start, edges = _chain_csr(start, edges)
+    L = lib()
+    n, nl = C.c_uint64(), C.c_uint64()
+    info = np.zeros(len(CHAIN_INFO), dtype=np.uint64)
+    err = C.create_string_buffer(512)
+    args = (_ptr(start), _ptr(edges), start.shape[0] - 2, edges.shape[0], rounds)
+    chain_cap, list_cap = min(edges.shape[0], 1 << 20), 2 * (start.shape[0] - 2)  # one call, unless the table is longer
+    while True:
+        ch = np.zeros(chain_cap, dtype=CHAIN_DTYPE)
+        reads, offs, ors = (np.zeros(list_cap, dtype=t) for t in (np.uint32, np.uint16, np.uint8))
+        rc = L.mgh_chains_build(*args, _ptr(ch), chain_cap, _ptr(reads), _ptr(offs), _ptr(ors), list_cap, C.byref(n),
+                                C.byref(nl), _ptr(info), err, 512)
+        if rc:
+            raise MgError(f"host chains failed ({rc}): {err.value.decode()}")
+        if n.value <= chain_cap and nl.value <= list_cap:
+            break
+        chain_cap, list_cap = max(chain_cap, n.value), max(list_cap, nl.value)
+    ch, reads, offs, ors = ch[: n.value], reads[: nl.value], offs[: nl.value], ors[: nl.value]
+    return Chains(ch, reads, offs, ors, info)
 
 
 def host_components(start: np.ndarray, disc: np.ndarray):
@@ -1207,7 +1325,13 @@ class UnitigGraph:
     mgh_graph_contract), on host C++.  main.cpp:48-50's sortEdges +
     saveGraphToFile are sort_edges() / save_unitig()."""
 
-    def __init__(self, rows: np.ndarray, lens: np.ndarray, min_overlap: int, track_locations: bool = True):
+    def __init__(self, rows: np.ndarray, lens: np.ndarray, min_overlap: int, track_locations: bool = True,
+                 chains=None):
+        """chains: None = the reference's loop alone; "host" = the safe chains of
+        the replayed graph from the host mirror contracted first; an
+        OverlapEngine = the same from the device (build_chains); a Chains = that
+        table (any subset of the safe chains; MgError -4 for anything else).
+        The contracted graph is the same in every field."""
         rows = np.ascontiguousarray(rows, dtype=EDGE_DTYPE)
         lens = np.ascontiguousarray(lens, dtype=np.uint16)
         L = self._L = lib()
@@ -1217,27 +1341,69 @@ class UnitigGraph:
                                 C.byref(self._g))
         if rc:
             raise MgError(f"graph replay failed ({rc})")
-        self._contract(t0, track_locations)
+        self._contract(t0, track_locations, chains, lens.shape[0])
 
     @classmethod
     def from_discoveries(cls, start: np.ndarray, disc: np.ndarray, lens: np.ndarray, min_overlap: int,
-                         track_locations: bool = True, components=None, threads: int = 0) -> "UnitigGraph":
+                         track_locations: bool = True, components=None, threads: int = 0,
+                         chains=None) -> "UnitigGraph":
         """The same graph from the per-read discovery lists (OverlapEngine.discoveries);
-        components / threads as in replay_discoveries."""
+        components / threads as in replay_discoveries; chains as in __init__."""
         self = cls.__new__(cls)
         self._L = lib()
         self._g = C.c_void_p()
         t0 = time.perf_counter()
         self._g = _replay_disc(start, disc, lens, min_overlap, components, threads)
-        self._contract(t0, track_locations)
+        self._contract(t0, track_locations, chains, np.asarray(lens).shape[0])
         return self
 
-    def _contract(self, t0: float, track_locations: bool):
+    @classmethod
+    def from_csr(cls, start: np.ndarray, edges: np.ndarray, track_locations: bool = True,
+                 chains=None) -> "UnitigGraph":
+        """The contraction of a graph given as a CSR (simple_csr's layout;
+        mgh_graph_from_csr), for graphs no discovery multiset produced; chains
+        as in __init__."""
+        start, edges = _chain_csr(start, edges)
+        self = cls.__new__(cls)
+        L = self._L = lib()
+        self._g = C.c_void_p()
+        t0 = time.perf_counter()
+        rc = L.mgh_graph_from_csr(_ptr(start), _ptr(edges), start.shape[0] - 2, edges.shape[0], C.byref(self._g))
+        if rc:
+            raise MgError(f"malformed CSR ({rc})")
+        self._contract(t0, track_locations, chains, start.shape[0] - 2)
+        return self
+
+    def _contract(self, t0: float, track_locations: bool, chains=None, n_reads: int = 0):
         L = self._L
         self.replay_nodes, self.replay_edges = int(L.mgh_graph_nodes(self._g)), int(L.mgh_graph_edges(self._g))
         t1 = time.perf_counter()
         it, merged, dead = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        rc = L.mgh_graph_contract(self._g, int(track_locations), C.byref(it), C.byref(merged), C.byref(dead))
+        self.chain_info = None
+        if chains is None:
+            rc = L.mgh_graph_contract(self._g, int(track_locations), C.byref(it), C.byref(merged), C.byref(dead))
+        else:
+            if not isinstance(chains, Chains):
+                csr = _graph_csr(self._g, n_reads)
+                if isinstance(chains, str) and chains == "host":
+                    chains = host_chains(*csr)
+                elif isinstance(chains, OverlapEngine):
+                    chains.build_chains(*csr)
+                    chains = chains.chains()
+                else:
+                    self.close()
+                    raise MgError("chains: None, \"host\", an OverlapEngine or a Chains")
+            self.chain_info = chains.info
+            ch = np.ascontiguousarray(chains.chains, dtype=CHAIN_DTYPE)
+            reads = np.ascontiguousarray(chains.reads, dtype=np.uint32)
+            offs = np.ascontiguousarray(chains.offs, dtype=np.uint16)
+            ors = np.ascontiguousarray(chains.ors, dtype=np.uint8)
+            if not (reads.shape[0] == offs.shape[0] == ors.shape[0]):
+                self.close()
+                raise MgError("chains: reads, offs and ors differ in length")
+            rc = L.mgh_graph_contract_chains(self._g, _ptr(ch), ch.shape[0], _ptr(reads), _ptr(offs), _ptr(ors),
+                                             reads.shape[0], int(track_locations), C.byref(it), C.byref(merged),
+                                             C.byref(dead))
         if rc:
             self.close()
             raise MgError(f"contraction failed ({rc})")
