@@ -361,6 +361,19 @@ class OverlapGraph {
   UINT64 getNumberOfPairedEdges() const { return pathCounters[3]; }
   // Until this is called the environment variable MG_DEVICE_PATHS decides (0 = host mirror).
   static void setDevicePaths(bool on);
+  // scaffolder (:2120-2223, main.cpp:85): every mate entry whose two reads lie
+  // uniquely on two different edges within mean + 3 SD supports that pair of
+  // edges; the pairs are sorted by support and every pair with support >= 3
+  // that no earlier merge freed is merged by mergeEdgesDisconnected.  Returns
+  // the number of pairs merged and writes the reference's line per merged pair
+  // to cout.  Needs calculateMeanAndSdOfInsertSize() first.  Twins and location
+  // lists come from the list state, as for findSupportByMatepairsAndMerge();
+  // the scoring runs in one device call (mg_scaffold_pairs), the merge loop on
+  // the host, and the Edge objects are rebuilt.  Without a HIP device, or with
+  // the device scaffolder off, the host mirror scores.  The same graph either way.
+  UINT64 scaffolder();
+  // Until this is called the environment variable MG_DEVICE_SCAFFOLD decides (0 = host mirror).
+  static void setDeviceScaffold(bool on);
   const mg_timings& timings() const { return lastTimings; }
 
  private:

@@ -366,6 +366,43 @@ int mgh_mate_paths(uint64_t n_reads, const mg_contig_edge* edges, const uint32_t
 int mgh_graph_merge_supported(mgh_graph* g, const mg_pair_support* pairs, uint64_t n, uint64_t min_support,
                               uint64_t* merged, char* err, uint64_t err_cap);
 
+/* --- scaffolder: OverlapGraph::scaffolder (OverlapGraph.cpp:2120-2223) with
+ * mergeEdgesDisconnected (:2386-2468).  The definitions of the scoring half
+ * are in include/mg_overlap.h ("scaffolder"). */
+/* The host mirror of mg_scaffold_pairs + mg_copy_scaffold_entries +
+ * mg_copy_scaffold_pairs over the same arrays (mg::scaffold_pairs), with the
+ * same -2 errors.  status: one MG_SCAF_* per mate entry; pairs: the first
+ * min(pair_cap, *n_pairs) records in first-seen order, as
+ * mg_copy_scaffold_pairs copies them (*n_pairs = all records, never more than
+ * the mate entries); counters[5] = the entries of each status.  Any output may be NULL.  0 = ok; -1 = bad arguments; -2 = see
+ * mg_scaffold_pairs. */
+int mgh_scaffold_pairs(uint64_t n_reads, const uint32_t* twin, uint64_t n_edges, const uint64_t* place_start,
+                       const mg_place* places, const uint64_t* mate_start, const mg_mate* mates,
+                       const uint64_t* mean, const uint64_t* sd, uint32_t n_datasets, uint8_t* status,
+                       mg_scaffold_pair* pairs, uint64_t pair_cap, uint64_t* n_pairs, uint64_t* counters, char* err,
+                       uint64_t err_cap);
+/* The merging half (:2197-2219) on a contracted or re-read handle: std::sort of
+ * the records by support (descending, pairedEdges::operator<), in the order
+ * given; then, for every record that no earlier merge freed and whose support
+ * is >= min_support (the reference: 3): distance /= support, the reference's
+ * "are supported" line, character for character (Flow is 0 on such a graph),
+ * and mergeEdgesDisconnected (:2386-2468): mergeEdges when dst(edge1) ==
+ * src(edge2) and matchEdgeType; otherwise findOverlap (:2368-2379) between the
+ * two nodes' strings, strands as at :2396-2397, over the packed reads in ID
+ * order (words: n_reads rows of words_per_read; lens), the merged lists of
+ * mergeListDisconnected with its UINT16 truncations, both new edges inserted
+ * and both old ones removed.  The pairs' edges index
+ * mgh_graph_contig_edges(all = 1) of the handle as it is now.  lines: at most
+ * lines_cap bytes are written, *lines_len = the bytes of all lines (at most 192
+ * per merged pair).  *merged = pairsOfEdgesMerged.  0 = ok; -1 = bad
+ * arguments; -4 = an orientation with no merged orientation; -5 = a pair that
+ * would be merged is one edge twice or an edge and its twin: a dry run finds
+ * it first, err names it and the graph is unchanged. */
+int mgh_graph_merge_scaffold(mgh_graph* g, const mg_scaffold_pair* pairs, uint64_t n, uint64_t min_support,
+                             const uint64_t* words, const uint16_t* lens, uint64_t n_reads, uint32_t words_per_read,
+                             char* lines, uint64_t lines_cap, uint64_t* lines_len, uint64_t* merged, char* err,
+                             uint64_t err_cap);
+
 #ifdef __cplusplus
 }
 #endif

@@ -552,6 +552,73 @@ int mg_copy_mate_paths(mg_ctx* ctx, uint8_t* status, uint32_t* visits, uint64_t*
                        uint8_t* flags, uint64_t path_cap);
 int mg_copy_path_pairs(mg_ctx* ctx, mg_pair_support* out, uint64_t cap, uint64_t* n_copied);
 
+/* --- scaffolder: the scoring half of OverlapGraph::scaffolder
+ * (OverlapGraph.cpp:2120-2195), one lane per mate entry.
+ *
+ * INPUTS as for mg_mate_paths, without the edges: twin[k] (the index of edge
+ * k's reverse edge), the placement CSR, the mate CSR, mean[d] and sd[d] per
+ * dataset.  place_start = NULL takes the resident placements of
+ * mg_build_placements, mate_start = NULL the resident mate lists.  Only lists
+ * that hold exactly one placement are ever read, so the resident (edge,
+ * position) order and the reference's list order give identical results.
+ *
+ * PER MATE ENTRY t = (A, j) holding (B, orient, d), t ascending in (A, j):
+ *   skipped (MG_SCAF_SKIPPED): A > B (:2137; A = B is processed, and there is
+ *     no mean[d] == 0 test here, unlike :1911).
+ *   A's list is its forward list iff orient is 0 or 1 (:2149; the opposite
+ *     choice to findPathBetweenMatepairs), B's iff orient is 0 or 2 (:2153).
+ *   not unique (MG_SCAF_NOT_UNIQUE): unless both lists hold exactly one
+ *     placement (:2157), (L1, loc1) and (L2, loc2).
+ *   far (MG_SCAF_FAR): dist = loc1 + loc2; unless dist < mean[d] + 3 sd[d]
+ *     (:2157).  All arithmetic is unsigned 64-bit and wraps; a dataset with
+ *     mean 0 and sd 0 therefore counts nothing.
+ *   same edge (MG_SCAF_SAME_EDGE): L1 == L2 or L1 == twin[L2] (:2161).
+ *   counted (MG_SCAF_COUNTED) otherwise: the entry joins the record that holds
+ *     (twin[L1], L2) or (twin[L2], L1) (:2168, :2174), adding 1 to its support
+ *     and dist to its distance (wrapping 64-bit sums); if there is none it
+ *     opens the record (edge1 = twin[L1], edge2 = L2) (:2184-2190).
+ * Records come in first-seen order (listOfPairedEdges before :2197).
+ *
+ * The record of an entry is found by its canonical key min(twin[L1] E + L2,
+ * twin[L2] E + L1), E = n_edges.  The two forms of one entry can never name
+ * the same record twice: they are equal only if twin[L1] == twin[L2] and L2 ==
+ * L1, which the same-edge test has excluded.  With twin an involution (every
+ * graph's is) the second form of an entry is the first form of the entry seen
+ * from the other strand, (a, b) -> (twin[b], twin[a]), so two entries share a
+ * key iff the reference's linear search finds the one's record for the other.
+ *
+ * mg_scaffold_pairs: validation first, in mg_mate_paths' order and wording, so
+ * nothing indexes with an unchecked value: -2 with mg_last_error naming the
+ * first twin outside the edges, else the first placement whose edge is
+ * outside the edges, else the first mate entry whose owner or mate ID lies
+ * outside 1..n_reads or whose dataset is not below n_datasets.  Then
+ * k_sc_score (status, key, dist per entry; the status counters leave a
+ * wavefront as one integer atomic each), a scan that compacts the counted
+ * entries in entry order, a stable radix sort of (key, index) over the bits
+ * E^2 needs, run heads, a 64-bit inclusive scan of dist in sorted order whose
+ * differences at the heads are the distances (exact modulo 2^64), and a sort of
+ * the heads by first index.  No floating point.  counters[5] = entries of each
+ * status, indexed by MG_SCAF_*; *n_pairs = records.  With no counted entry no
+ * sort is launched.  -1: bad arguments, a malformed CSR, a sharded or
+ * exchange-mode context, 2^31 or more edges, placements or entries. */
+enum { MG_SCAF_SKIPPED = 0, MG_SCAF_NOT_UNIQUE = 1, MG_SCAF_FAR = 2, MG_SCAF_SAME_EDGE = 3, MG_SCAF_COUNTED = 4 };
+typedef struct mg_scaffold_pair {
+  uint32_t edge1, edge2; /* indices into the edges, in the orientation first seen */
+  uint64_t support;
+  uint64_t distance; /* the sum of dist over the record's entries (mod 2^64) */
+} mg_scaffold_pair;
+int mg_scaffold_pairs(mg_ctx* ctx, const uint32_t* twin, uint64_t n_edges, uint64_t n_reads,
+                      const uint64_t* place_start, const mg_place* places, const uint64_t* mate_start,
+                      const mg_mate* mates, const uint64_t* mean, const uint64_t* sd, uint32_t n_datasets,
+                      uint64_t counters[5], uint64_t* n_pairs, float* device_ms);
+/* status: one MG_SCAF_* per mate entry of the last mg_scaffold_pairs. */
+int mg_copy_scaffold_entries(mg_ctx* ctx, uint8_t* status);
+int mg_copy_scaffold_pairs(mg_ctx* ctx, mg_scaffold_pair* out, uint64_t cap, uint64_t* n_copied);
+/* Sizes and times of the last mg_scaffold_pairs: out[3] = mate entries,
+ * counted entries, records; ms[2] = the score kernel, the aggregate (device
+ * time by events).  Either may be NULL. */
+int mg_scaffold_info(mg_ctx* ctx, uint64_t* out, float* ms);
+
 /* --- sharding (multi-GPU, one process per GPU) ---------------------------- */
 /* Restrict this context to index buckets owned by `rank` of `nranks`
  * (bucket-range sharding) and/or to the source reads with

@@ -4,7 +4,8 @@
 // per-read discovery lists D(A); mg_comp.hip: their components; mg_mates.hip:
 // read lookup and the per-read mate lists; mg_contigs.hip: the strings of edges;
 // mg_places.hip: read placements, insert sizes and edge coverage; mg_paths.hip:
-// mate-pair paths; mg_chains.hip: safe chains of a replayed graph).  The core
+// mate-pair paths; mg_scaffold.hip: scaffolder support; mg_chains.hip: safe
+// chains of a replayed graph).  The core
 // fields of mg_ctx belong to mg_kernels.hip; each
 // derived stage keeps its state in one struct (DiscStage .. ChainStage: ready
 // flag, counts, test options, buffers, EventPair) that mg_ctx embeds by value.
@@ -211,6 +212,18 @@ struct PathStage {
   // "path_budget" (work units per mate entry, 0 = 2^16)
   uint64_t batch = 0, budget = 0;
   float explore_ms = 0.f, aggregate_ms = 0.f;
+  EventPair ev;
+};
+
+// scaffolder support (mg_scaffold.hip, mg_scaffold_pairs): per mate entry its
+// status, and the supported edge pairs with support and summed distance.
+// ready until the next mg_scaffold_pairs
+struct ScaffoldStage {
+  bool ready = false;
+  uint64_t n_entries = 0, n_counted = 0, n_pairs = 0;
+  DevArray<uint8_t> status;  // per entry: MG_SCAF_*
+  DevArray<mg_scaffold_pair> pairs;
+  float score_ms = 0.f, aggregate_ms = 0.f;
   EventPair ev;
 };
 
@@ -522,6 +535,7 @@ struct mg_ctx {
   ContigStage contigs;
   PlaceStage places;
   PathStage paths;
+  ScaffoldStage scaffold;
   ChainStage chains;
 };
 

@@ -9,7 +9,8 @@
 //   OverlapGraph::exploreGraph                     OverlapGraph.cpp:1781-1870
 //
 // mg_mate_paths (one stream):
-//   k_pt_edges / k_pt_places / k_pt_mates : validation, the first offender of
+//   k_pt_edges / k_check_places / k_mate_owners (the last two in mg_stage.hpp,
+//                 shared with mg_scaffold_pairs): validation, the first offender of
 //                 each kind kept by atomicMin; per edge its adjacency range
 //                 graph[dst] by two lower bounds over src; per mate entry its owner;
 //   k_pt_explore: lane per mate entry, `path_batch` entries per launch.  The
@@ -22,7 +23,7 @@
 //                 "path space" behind the earlier batches';
 //   aggregate   : k_pt_select (flagged positions whose pair is not two
 //                 self-loops) -> ExclusiveSum -> k_pt_emit (canonical key,
-//                 position) -> stable SortPairs by key -> k_pt_heads ->
+//                 position) -> stable SortPairs by key -> k_run_heads ->
 //                 ExclusiveSum -> k_pt_headrec (first position, run length by
 //                 an upper bound) -> SortPairs by first position -> k_pt_pairs.
 //                 Positions ascend in (entry, k), so a run's first position is
@@ -69,16 +70,6 @@ struct Work {
 };
 #define W_(arr, level) w.arr[(uint64_t)(level) * w.lanes + ln]
 
-// last k in [lo, hi) with base[k] <= x (base[lo] <= x)
-__device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ base, uint64_t lo, uint64_t hi, uint64_t x) {
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (base[mid] <= x) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
-
 __device__ __forceinline__ bool match_edge_type(uint32_t a, uint32_t b) {  // matchEdgeType :19-26
   return ((a == 1 || a == 3) && (b == 2 || b == 3)) || ((a == 0 || a == 2) && (b == 0 || b == 1));
 }
@@ -103,24 +94,6 @@ __global__ __launch_bounds__(kThreads) void k_pt_edges(const mg_contig_edge* __r
     b[s] = lo;
   }
   er[k] = EdgeRec{e.offset, (uint32_t)b[0], (uint32_t)b[1], e.orient, e.src == e.dst ? 1u : 0u};
-}
-
-__global__ __launch_bounds__(kThreads) void k_pt_places(const mg_place* __restrict__ places, uint64_t P, uint64_t n,
-                                                        ull* __restrict__ ctl) {
-  const uint64_t p = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (p < P && places[p].edge >= n) atomicMin(&ctl[2], (ull)p);
-}
-
-__global__ __launch_bounds__(kThreads) void k_pt_mates(const uint64_t* __restrict__ mstart,
-                                                       const mg_mate* __restrict__ mates, uint64_t M, uint64_t N,
-                                                       uint32_t n_datasets, uint32_t* __restrict__ owner,
-                                                       ull* __restrict__ ctl) {
-  const uint64_t m = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (m >= M) return;
-  const uint64_t a = last_le(mstart, 0, N + 2, m);  // mstart[a] <= m < mstart[a + 1]
-  const mg_mate mt = mates[m];
-  if (a < 1 || a > N || mt.id < 1 || mt.id > N || mt.dataset >= n_datasets) atomicMin(&ctl[3], (ull)m);
-  owner[m] = (uint32_t)a;
 }
 
 // exploreGraph (:1781-1870) from level 0 for lane ln; the number of paths
@@ -345,13 +318,6 @@ __global__ __launch_bounds__(kThreads) void k_pt_emit(const uint32_t* __restrict
   vals[idx[p]] = (uint32_t)p;
 }
 
-__global__ __launch_bounds__(kThreads) void k_pt_heads(const uint64_t* __restrict__ keys, uint64_t F,
-                                                       uint32_t* __restrict__ head) {
-  const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i > F) return;
-  head[i] = i < F && (i == 0 || keys[i] != keys[i - 1]);
-}
-
 __global__ __launch_bounds__(kThreads) void k_pt_headrec(const uint64_t* __restrict__ keys,
                                                          const uint32_t* __restrict__ vals, uint64_t F,
                                                          const uint32_t* __restrict__ head,
@@ -400,12 +366,6 @@ int grow_keep(mg_ctx* ctx, DevArray<T>& a, size_t used, size_t need, size_t targ
   return 0;
 }
 
-int bits_of(uint64_t x) {  // bits that hold every value <= x (at least 1)
-  int b = 1;
-  while (b < 64 && (x >> b)) ++b;
-  return b;
-}
-
 }  // namespace
 
 extern "C" {
@@ -428,52 +388,18 @@ int mg_mate_paths(mg_ctx* ctx, const mg_contig_edge* edges, const uint32_t* twin
   if (n_edges >> 31) return set_err(ctx, "mg_mate_paths: 2^31 or more edges are not supported");
   MG_TRY(hipSetDevice(ctx->device));
   if (whole_multiset(ctx, "mg_mate_paths")) return -1;
-  const uint64_t N = n_reads, entries = N + 2;
+  const uint64_t N = n_reads;
   hipStream_t st = ctx->stream;
 
   // the two CSRs: the caller's in scratch, or the resident ones
-  Scratch<uint64_t> d_ps, d_ms;
-  Scratch<mg_place> d_pl;
-  Scratch<mg_mate> d_mt;
-  const uint64_t* pstart = ctx->places.start.p;
-  const mg_place* prec = ctx->places.recs.p;
-  uint64_t P0 = ctx->places.n;
-  if (place_start) {
-    if (place_start[0] != 0) return set_err(ctx, "mg_mate_paths: place_start[0] must be 0");
-    for (uint64_t a = 0; a + 1 < entries; ++a)
-      if (place_start[a + 1] < place_start[a]) return set_err(ctx, "mg_mate_paths: place_start must not decrease");
-    P0 = place_start[entries - 1];
-    if (P0 && !places) return set_err(ctx, "mg_mate_paths: null argument");
-    MG_SCRATCH(d_ps, entries, "caller's placement starts");
-    MG_SCRATCH(d_pl, P0, "caller's placements");
-    MG_TRY(hipMemcpyAsync(d_ps.p, place_start, entries * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (P0) MG_TRY(hipMemcpyAsync(d_pl.p, places, P0 * sizeof(mg_place), hipMemcpyHostToDevice, st));
-    pstart = d_ps.p;
-    prec = d_pl.p;
-  } else if (!ctx->places.ready || ctx->n != N || ctx->places.edges.size() != n_edges) {
-    return set_err(ctx, "mg_mate_paths: no resident placements of n_reads reads on n_edges edges: "
-                        "mg_build_placements must run for these edges first, or pass a CSR");
-  }
-  const uint64_t* mstart = ctx->mates.start.p;
-  const mg_mate* mrec = ctx->mates.recs.p;
-  uint64_t M = ctx->mates.n;
-  if (mate_start) {
-    if (mate_start[0] != 0) return set_err(ctx, "mg_mate_paths: mate_start[0] must be 0");
-    for (uint64_t a = 0; a + 1 < entries; ++a)
-      if (mate_start[a + 1] < mate_start[a]) return set_err(ctx, "mg_mate_paths: mate_start must not decrease");
-    M = mate_start[entries - 1];
-    if (M && !mates) return set_err(ctx, "mg_mate_paths: null argument");
-    MG_SCRATCH(d_ms, entries, "caller's mate list starts");
-    MG_SCRATCH(d_mt, M, "caller's mate lists");
-    MG_TRY(hipMemcpyAsync(d_ms.p, mate_start, entries * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    if (M) MG_TRY(hipMemcpyAsync(d_mt.p, mates, M * sizeof(mg_mate), hipMemcpyHostToDevice, st));
-    mstart = d_ms.p;
-    mrec = d_mt.p;
-  } else if (!ctx->mates.ready || ctx->n != N) {
-    return set_err(ctx, "mg_mate_paths: no resident mate lists of n_reads reads: mg_build_mate_pairs must run for "
-                        "the current reads first, or pass a CSR");
-  }
-  if ((P0 >> 31) || (M >> 31)) return set_err(ctx, "mg_mate_paths: 2^31 or more placements or mate entries are not supported");
+  PairCsrs csr;
+  if (const int rc = csr.take(ctx, "mg_mate_paths", N, n_edges, place_start, places, mate_start, mates)) return rc;
+  const uint64_t* pstart = csr.pstart;
+  const mg_place* prec = csr.prec;
+  const uint64_t P0 = csr.P;
+  const uint64_t* mstart = csr.mstart;
+  const mg_mate* mrec = csr.mrec;
+  const uint64_t M = csr.M;
 
   Scratch<mg_contig_edge> d_edges;
   Scratch<uint32_t> d_twin, d_owner;
@@ -505,12 +431,12 @@ int mg_mate_paths(mg_ctx* ctx, const mg_contig_edge* edges, const uint32_t* twin
     MG_TRY(hipGetLastError());
   }
   if (P0) {
-    hipLaunchKernelGGL(k_pt_places, dim3(blocks_for(P0)), dim3(kThreads), 0, st, prec, P0, n_edges, ctl.p);
+    hipLaunchKernelGGL(k_check_places<ull>, dim3(blocks_for(P0)), dim3(kThreads), 0, st, prec, P0, n_edges, ctl.p + 2);
     MG_TRY(hipGetLastError());
   }
   if (M) {
-    hipLaunchKernelGGL(k_pt_mates, dim3(blocks_for(M)), dim3(kThreads), 0, st, mstart, mrec, M, N, n_datasets,
-                       d_owner.p, ctl.p);
+    hipLaunchKernelGGL(k_mate_owners<ull>, dim3(blocks_for(M)), dim3(kThreads), 0, st, mstart, mrec, M, N, n_datasets,
+                       d_owner.p, ctl.p + 3);
     MG_TRY(hipGetLastError());
   }
   ull bad[4] = {~0ull, ~0ull, ~0ull, ~0ull};
@@ -524,18 +450,8 @@ int mg_mate_paths(mg_ctx* ctx, const mg_contig_edge* edges, const uint32_t* twin
                " is not below " + std::to_string(n_edges) + " (-2)";
     return -2;
   }
-  if (bad[2] != ~0ull) {
-    mg_place pl{0, 0, 0};
-    MG_TRY(hipMemcpy(&pl, prec + bad[2], sizeof(mg_place), hipMemcpyDeviceToHost));
-    ctx->err = "mg_mate_paths: placement " + std::to_string(bad[2]) + ": its edge " + std::to_string(pl.edge) +
-               " is not below " + std::to_string(n_edges) + " (-2)";
-    return -2;
-  }
-  if (bad[3] != ~0ull) {
-    ctx->err = "mg_mate_paths: mate entry " + std::to_string(bad[3]) + ": its dataset is not below " +
-               std::to_string(n_datasets) + " or its owner or mate ID lies outside 1.." + std::to_string(N) + " (-2)";
-    return -2;
-  }
+  if (bad[2] != ~0ull) return bad_place(ctx, "mg_mate_paths", prec, bad[2], n_edges);
+  if (bad[3] != ~0ull) return bad_mate(ctx, "mg_mate_paths", bad[3], n_datasets, N);
 
   // --- explore, a batch of lanes at a time
   const uint64_t batch = std::max<uint64_t>(1, std::min<uint64_t>(ps.batch ? ps.batch : kDefaultBatch, std::max<uint64_t>(M, 1)));
@@ -641,7 +557,7 @@ int mg_mate_paths(mg_ctx* ctx, const mg_contig_edge* edges, const uint32_t* twin
       size_t t2 = tb2;
       MG_TRY(hipcub::DeviceRadixSort::SortPairs(tmp2.p, t2, keys_a.p, keys_b.p, vals_a.p, vals_b.p, (int)F, 0, key_bits,
                                                 st));
-      hipLaunchKernelGGL(k_pt_heads, dim3(blocks_for(F + 1)), dim3(kThreads), 0, st, keys_b.p, F, head.p);
+      hipLaunchKernelGGL(k_run_heads<uint64_t>, dim3(blocks_for(F + 1)), dim3(kThreads), 0, st, keys_b.p, F, head.p);
       MG_TRY(hipGetLastError());
       t2 = tb2;
       MG_TRY(hipcub::DeviceScan::ExclusiveSum(tmp2.p, t2, head.p, hidx.p, (int64_t)(F + 1), st));

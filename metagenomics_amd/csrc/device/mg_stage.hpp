@@ -1,9 +1,11 @@
 // mg_stage.hpp — INTERNAL: what the derived-stage translation units share
 // beyond the context (mg_dataset.hip, mg_disc.hip, mg_comp.hip, mg_mates.hip,
-// mg_contigs.hip, mg_places.hip, mg_chains.hip): the view of the resident reads, the launch
-// grid, the CSR starts of sorted owners, control words, the copy tail of the
-// mg_copy_* calls and the edge lists that mg_build_contigs and
-// mg_build_placements both take.  (DevArray, Scratch and their growth macros
+// mg_contigs.hip, mg_places.hip, mg_paths.hip, mg_scaffold.hip, mg_chains.hip): the view
+// of the resident reads, the launch grid, the CSR starts of sorted owners,
+// control words, the copy tail of the mg_copy_* calls, the edge lists that
+// mg_build_contigs and mg_build_placements both take, and the CSR inputs and
+// validation kernels that mg_mate_paths and mg_scaffold_pairs both take.
+// (DevArray, Scratch and their growth macros
 // are in mg_ctx.hpp.)  mg_kernels.hip does not include it.
 #ifndef MG_STAGE_HPP_
 #define MG_STAGE_HPP_
@@ -130,6 +132,134 @@ struct EdgeLists {
     MG_TRY(hipMemcpyAsync(reads.p, h_reads, n_list * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
     MG_TRY(hipMemcpyAsync(offs.p, h_offs, n_list * sizeof(uint16_t), hipMemcpyHostToDevice, ctx->stream));
     MG_TRY(hipMemcpyAsync(ors.p, h_ors, n_list, hipMemcpyHostToDevice, ctx->stream));
+    return 0;
+  }
+};
+
+// --- what mg_mate_paths and mg_scaffold_pairs share: the two CSRs they read,
+// the validation of placements and mate entries, run heads of sorted keys ---
+
+// last k in [lo, hi) with base[k] <= x (base[lo] <= x)
+__device__ __forceinline__ uint64_t last_le(const uint64_t* __restrict__ base, uint64_t lo, uint64_t hi, uint64_t x) {
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (base[mid] <= x) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+
+// (templates, as k_csr_starts: only the files that launch them carry them)
+// *bad = the first placement whose edge is not below n
+template <typename Ctl>
+__global__ __launch_bounds__(kThreads) void k_check_places(const mg_place* __restrict__ places, uint64_t P, uint64_t n,
+                                                           Ctl* __restrict__ bad) {
+  const uint64_t p = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (p < P && places[p].edge >= n) atomicMin(bad, (Ctl)p);
+}
+
+// owner[m] = the read whose list holds mate entry m; *bad = the first entry
+// whose owner or mate ID lies outside 1..N or whose dataset is not below n_datasets
+template <typename Ctl>
+__global__ __launch_bounds__(kThreads) void k_mate_owners(const uint64_t* __restrict__ mstart,
+                                                          const mg_mate* __restrict__ mates, uint64_t M, uint64_t N,
+                                                          uint32_t n_datasets, uint32_t* __restrict__ owner,
+                                                          Ctl* __restrict__ bad) {
+  const uint64_t m = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (m >= M) return;
+  const uint64_t a = last_le(mstart, 0, N + 2, m);  // mstart[a] <= m < mstart[a + 1]
+  const mg_mate mt = mates[m];
+  if (a < 1 || a > N || mt.id < 1 || mt.id > N || mt.dataset >= n_datasets) atomicMin(bad, (Ctl)m);
+  owner[m] = (uint32_t)a;
+}
+
+// head[i] = 1 where sorted key i starts a run, for i in [0, F]; head[F] = 0 (the scan's total slot)
+template <typename Key>
+__global__ __launch_bounds__(kThreads) void k_run_heads(const Key* __restrict__ keys, uint64_t F,
+                                                        uint32_t* __restrict__ head) {
+  const uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i > F) return;
+  head[i] = i < F && (i == 0 || keys[i] != keys[i - 1]);
+}
+
+inline int bits_of(uint64_t x) {  // bits that hold every value <= x (at least 1)
+  int b = 1;
+  while (b < 64 && (x >> b)) ++b;
+  return b;
+}
+
+// the -2 messages of the two checks above (`who` = the entry point's name)
+inline int bad_place(mg_ctx* ctx, const char* who, const mg_place* d_places, uint64_t p, uint64_t n_edges) {
+  mg_place pl{0, 0, 0};
+  MG_TRY(hipMemcpy(&pl, d_places + p, sizeof(mg_place), hipMemcpyDeviceToHost));
+  ctx->err = std::string(who) + ": placement " + std::to_string(p) + ": its edge " + std::to_string(pl.edge) +
+             " is not below " + std::to_string(n_edges) + " (-2)";
+  return -2;
+}
+inline int bad_mate(mg_ctx* ctx, const char* who, uint64_t m, uint32_t n_datasets, uint64_t n_reads) {
+  ctx->err = std::string(who) + ": mate entry " + std::to_string(m) + ": its dataset is not below " +
+             std::to_string(n_datasets) + " or its owner or mate ID lies outside 1.." + std::to_string(n_reads) + " (-2)";
+  return -2;
+}
+
+// The placement CSR and the mate CSR of one call: the caller's, uploaded to
+// scratch and checked (starts from 0, never decreasing), or, for a NULL start
+// array, the resident ones of mg_build_placements (for n_edges edges) and
+// mg_build_mate_pairs.  Fewer than 2^31 records each.
+struct PairCsrs {
+  Scratch<uint64_t> d_ps, d_ms;
+  Scratch<mg_place> d_pl;
+  Scratch<mg_mate> d_mt;
+  const uint64_t* pstart = nullptr;
+  const mg_place* prec = nullptr;
+  uint64_t P = 0;
+  const uint64_t* mstart = nullptr;
+  const mg_mate* mrec = nullptr;
+  uint64_t M = 0;
+
+  int take(mg_ctx* ctx, const std::string& who, uint64_t n_reads, uint64_t n_edges, const uint64_t* place_start,
+           const mg_place* places, const uint64_t* mate_start, const mg_mate* mates) {
+    const uint64_t N = n_reads, entries = N + 2;
+    hipStream_t st = ctx->stream;
+    pstart = ctx->places.start.p;
+    prec = ctx->places.recs.p;
+    P = ctx->places.n;
+    if (place_start) {
+      if (place_start[0] != 0) return set_err(ctx, who + ": place_start[0] must be 0");
+      for (uint64_t a = 0; a + 1 < entries; ++a)
+        if (place_start[a + 1] < place_start[a]) return set_err(ctx, who + ": place_start must not decrease");
+      P = place_start[entries - 1];
+      if (P && !places) return set_err(ctx, who + ": null argument");
+      MG_SCRATCH(d_ps, entries, "caller's placement starts");
+      MG_SCRATCH(d_pl, P, "caller's placements");
+      MG_TRY(hipMemcpyAsync(d_ps.p, place_start, entries * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      if (P) MG_TRY(hipMemcpyAsync(d_pl.p, places, P * sizeof(mg_place), hipMemcpyHostToDevice, st));
+      pstart = d_ps.p;
+      prec = d_pl.p;
+    } else if (!ctx->places.ready || ctx->n != N || ctx->places.edges.size() != n_edges) {
+      return set_err(ctx, who + ": no resident placements of n_reads reads on n_edges edges: "
+                                "mg_build_placements must run for these edges first, or pass a CSR");
+    }
+    mstart = ctx->mates.start.p;
+    mrec = ctx->mates.recs.p;
+    M = ctx->mates.n;
+    if (mate_start) {
+      if (mate_start[0] != 0) return set_err(ctx, who + ": mate_start[0] must be 0");
+      for (uint64_t a = 0; a + 1 < entries; ++a)
+        if (mate_start[a + 1] < mate_start[a]) return set_err(ctx, who + ": mate_start must not decrease");
+      M = mate_start[entries - 1];
+      if (M && !mates) return set_err(ctx, who + ": null argument");
+      MG_SCRATCH(d_ms, entries, "caller's mate list starts");
+      MG_SCRATCH(d_mt, M, "caller's mate lists");
+      MG_TRY(hipMemcpyAsync(d_ms.p, mate_start, entries * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+      if (M) MG_TRY(hipMemcpyAsync(d_mt.p, mates, M * sizeof(mg_mate), hipMemcpyHostToDevice, st));
+      mstart = d_ms.p;
+      mrec = d_mt.p;
+    } else if (!ctx->mates.ready || ctx->n != N) {
+      return set_err(ctx, who + ": no resident mate lists of n_reads reads: mg_build_mate_pairs must run for "
+                                "the current reads first, or pass a CSR");
+    }
+    if ((P >> 31) || (M >> 31)) return set_err(ctx, who + ": 2^31 or more placements or mate entries are not supported");
     return 0;
   }
 };

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <fstream>
 #include <iomanip>
+#include <iostream>
 #include <sstream>
 #include <thread>
 #include <unordered_map>
@@ -22,6 +23,7 @@
 #include "mg_mates.hpp"
 #include "mg_parse.hpp"
 #include "mg_paths.hpp"
+#include "mg_scaffold.hpp"
 #include "mg_places.hpp"
 #include "mg_unitig.hpp"
 #include "mg_graph.hpp"
@@ -984,6 +986,92 @@ UINT64 OverlapGraph::findSupportByMatepairsAndMerge() {
   pathCounters[1] = counters[1];
   pathCounters[2] = counters[2];
   pathCounters[3] = pairs.size();
+  materialize();
+  return merged;
+}
+
+namespace {
+// g_device_scaffold: OverlapGraph::setDeviceScaffold; -1 = not called, the
+// environment variable MG_DEVICE_SCAFFOLD decides (unset: device)
+int g_device_scaffold = -1;
+
+bool use_device_scaffold(UINT64 n_reads) {
+  const char* v = std::getenv("MG_DEVICE_SCAFFOLD");
+  const bool on = g_device_scaffold < 0 ? (v && *v ? std::atoi(v) != 0 : true) : g_device_scaffold != 0;
+  return on && n_reads && mg_device_count() > 0;
+}
+}  // namespace
+
+void OverlapGraph::setDeviceScaffold(bool on) { g_device_scaffold = on ? 1 : 0; }
+
+UINT64 OverlapGraph::scaffolder() {
+  const char* who = "scaffolder";
+  if (!dataSet) throw mg::Error(std::string(who) + ": no Dataset");
+  adoptEdgeLists();
+  if (!unitig) throw mg::Error(std::string(who) + ": no replayed graph");
+  const uint32_t D = (uint32_t)dataSet->pairedEndDatasetFileNames.size();
+  if (meanOfInsertSizes.size() != D || sdOfInsertSizes.size() != D)
+    throw mg::Error(std::string(who) + ": calculateMeanAndSdOfInsertSize must run first");
+  const UINT64 N = dataSet->getNumberOfUniqueReads();
+  if (!unitig->track || unitig->loc_fwd.size() != N + 1 || unitig->loc_rev.size() != N + 1)
+    throw mg::Error(std::string(who) + ": the graph keeps no read locations");
+  // the twins and the location lists in list order, as mgh_graph_edge_twins / _location_lists give them
+  mg::ContigLists c;
+  mg::contig_edges(*unitig, true, &c);
+  std::vector<uint32_t> index(unitig->pool.size(), 0xFFFFFFFFu);
+  for (size_t k = 0; k < c.pool.size(); ++k) index[c.pool[k]] = (uint32_t)k;
+  std::vector<uint32_t> twin(c.pool.size());
+  for (size_t k = 0; k < c.pool.size(); ++k) twin[k] = index[unitig->pool[c.pool[k]].rev];
+  std::vector<uint64_t> pstart(N + 2, 0);
+  std::vector<mg_place> places;
+  for (UINT64 r = 1; r <= N; ++r) {
+    pstart[r] = places.size();
+    for (int side = 0; side < 2; ++side)
+      for (const mg::ReadLoc& l : side ? unitig->loc_rev[r] : unitig->loc_fwd[r])
+        places.push_back(mg_place{index[l.edge], side ? 0u : 1u, l.loc});
+  }
+  pstart[N + 1] = places.size();
+  std::vector<uint64_t> mstart(N + 2, 0);
+  std::vector<mg_mate> mates(dataSet->mates.size());
+  if (dataSet->mateStart.size() == N + 2) mstart = dataSet->mateStart;
+  else mates.clear();
+  for (size_t i = 0; i < mates.size(); ++i)
+    mates[i] = mg_mate{(uint32_t)dataSet->mates[i].matePairID, dataSet->mates[i].matePairOrientation,
+                       dataSet->mates[i].datasetNumber, 0};
+  const std::vector<uint64_t> mean(meanOfInsertSizes.begin(), meanOfInsertSizes.end());
+  const std::vector<uint64_t> sd(sdOfInsertSizes.begin(), sdOfInsertSizes.end());
+  mg::ScaffoldInput in;
+  in.n_reads = N;
+  in.twin = twin.data();
+  in.n_edges = twin.size();
+  in.place_start = pstart.data();
+  in.places = places.data();
+  in.mate_start = mstart.data();
+  in.mates = mates.data();
+  in.mean = mean.data();
+  in.sd = sd.data();
+  in.n_datasets = D;
+  std::string err;
+  std::vector<mg_scaffold_pair> pairs;
+  if (use_device_scaffold(N)) {
+    PlaceCtx pc(hashTable, dataSet, who);
+    uint64_t counters[5], n_pairs = 0, copied = 0;
+    if (mg_scaffold_pairs(pc.ctx, in.twin, in.n_edges, N, in.place_start, in.places, in.mate_start, in.mates, in.mean,
+                          in.sd, D, counters, &n_pairs, nullptr))
+      throw mg::Error(std::string(who) + ": " + mg_last_error(pc.ctx));
+    pairs.resize(n_pairs);
+    if (mg_copy_scaffold_pairs(pc.ctx, pairs.data(), n_pairs, &copied) || copied != n_pairs)
+      throw mg::Error(std::string(who) + ": " + mg_last_error(pc.ctx));
+  } else {
+    std::vector<uint8_t> status;
+    if (mg::scaffold_pairs(in, &status, &pairs, nullptr, &err)) throw mg::Error(std::string(who) + ": " + err);
+  }
+  uint64_t merged = 0;
+  std::string lines;
+  if (mg::merge_scaffold(unitig, c.pool, pairs.data(), pairs.size(), 3, dataSet->packedWords(), dataSet->packedLengths(),
+                         N, dataSet->wordsPerRead(), &lines, &merged, &err))
+    throw mg::Error(std::string(who) + ": " + err);
+  std::cout << lines;
   materialize();
   return merged;
 }
@@ -2206,6 +2294,67 @@ int mgh_graph_merge_supported(mgh_graph* g, const mg_pair_support* pairs, uint64
     std::string e;
     const int rc = mg::merge_supported(g->u.get(), pool_of, pairs, n, min_support, merged, &e);
     if (rc) put_err(e, err, err_cap);
+    return rc;
+  } catch (const std::exception&) {
+    return -1;
+  }
+}
+
+int mgh_scaffold_pairs(uint64_t n_reads, const uint32_t* twin, uint64_t n_edges, const uint64_t* place_start,
+                       const mg_place* places, const uint64_t* mate_start, const mg_mate* mates,
+                       const uint64_t* mean, const uint64_t* sd, uint32_t n_datasets, uint8_t* status,
+                       mg_scaffold_pair* pairs, uint64_t pair_cap, uint64_t* n_pairs, uint64_t* counters, char* err,
+                       uint64_t err_cap) {
+  put_err("", err, err_cap);
+  if (n_pairs) *n_pairs = 0;
+  try {
+    mg::ScaffoldInput in;
+    in.n_reads = n_reads;
+    in.twin = twin;
+    in.n_edges = n_edges;
+    in.place_start = place_start;
+    in.places = places;
+    in.mate_start = mate_start;
+    in.mates = mates;
+    in.mean = mean;
+    in.sd = sd;
+    in.n_datasets = n_datasets;
+    std::string e;
+    std::vector<uint8_t> st;
+    std::vector<mg_scaffold_pair> pr;
+    uint64_t cnt[5];
+    const int rc = mg::scaffold_pairs(in, &st, &pr, cnt, &e);
+    if (rc) {
+      put_err(e, err, err_cap);
+      return rc;
+    }
+    if (status) std::copy(st.begin(), st.end(), status);
+    if (pairs) std::copy(pr.begin(), pr.begin() + std::min<uint64_t>(pair_cap, pr.size()), pairs);
+    if (n_pairs) *n_pairs = pr.size();
+    if (counters) std::copy(cnt, cnt + 5, counters);
+  } catch (const std::exception&) {
+    return -1;
+  }
+  return 0;
+}
+
+int mgh_graph_merge_scaffold(mgh_graph* g, const mg_scaffold_pair* pairs, uint64_t n, uint64_t min_support,
+                             const uint64_t* words, const uint16_t* lens, uint64_t n_reads, uint32_t words_per_read,
+                             char* lines, uint64_t lines_cap, uint64_t* lines_len, uint64_t* merged, char* err,
+                             uint64_t err_cap) {
+  put_err("", err, err_cap);
+  if (merged) *merged = 0;
+  if (lines_len) *lines_len = 0;
+  if (!g || !g->u) return -1;
+  try {
+    std::vector<uint32_t> pool_of, index;
+    edge_indices(*g->u, &pool_of, &index);
+    std::string e, text;
+    const int rc = mg::merge_scaffold(g->u.get(), pool_of, pairs, n, min_support, words, lens, n_reads, words_per_read,
+                                      &text, merged, &e);
+    if (rc) put_err(e, err, err_cap);
+    if (lines && lines_cap) std::memcpy(lines, text.data(), std::min<uint64_t>(lines_cap, text.size()));
+    if (lines_len) *lines_len = text.size();
     return rc;
   } catch (const std::exception&) {
     return -1;

@@ -360,6 +360,64 @@ void UnitigGraph::merge(uint32_t e1, uint32_t e2) {  // mergeEdges :704-759
   if (pool[e2].flow == 0 || flow == 0) remove(e2);
 }
 
+void UnitigGraph::merge_list_disconnected(uint32_t e1, uint32_t e2, uint64_t overlap_offset,
+                                          EdgeReads& out) const {  // mergeListDisconnected :2476-2512
+  uint64_t sum = 0;
+  if (reads[e1]) {
+    const EdgeReads& a = *reads[e1];
+    out.reads = a.reads;
+    out.offs = a.offs;
+    out.ors = a.ors;
+    for (uint16_t o : a.offs) sum += o;
+  }
+  out.reads.push_back(pool[e1].dst);
+  out.offs.push_back((uint16_t)(pool[e1].offset - sum));  // (UINT16 push_back of a UINT64, :2488)
+  out.ors.push_back((pool[e1].orient == 1 || pool[e1].orient == 3) ? 1 : 0);
+  out.reads.push_back(pool[e2].src);
+  out.offs.push_back((uint16_t)overlap_offset);  // (:2496; gapLength stays unused)
+  out.ors.push_back((pool[e2].orient == 2 || pool[e2].orient == 3) ? 1 : 0);
+  if (reads[e2]) {
+    const EdgeReads& b = *reads[e2];
+    out.reads.insert(out.reads.end(), b.reads.begin(), b.reads.end());
+    out.offs.insert(out.offs.end(), b.offs.begin(), b.offs.end());
+    out.ors.insert(out.ors.end(), b.ors.begin(), b.ors.end());
+  }
+}
+
+void UnitigGraph::merge_edges_disconnected(uint32_t e1, uint32_t e2, uint64_t offset1,
+                                           uint64_t offset2) {  // mergeEdgesDisconnected :2401-2467
+  const uint8_t o1 = pool[e1].orient, o2 = pool[e2].orient;
+  if (o1 > 3 || o2 > 3) {  // mergedEdgeOrientationDisconnected :2520-2537, the MYEXIT branch
+    bad_merge = true;
+    return;
+  }
+  const uint8_t of = (uint8_t)((o1 >= 2 ? 2 : 0) + ((o2 & 1) ? 1 : 0));
+  const uint8_t orr = twin_orient(of);
+  const uint32_t r1 = pool[e1].src, r2 = pool[e2].dst;
+  const uint32_t e1r = pool[e1].rev, e2r = pool[e2].rev;
+  auto lf = std::make_unique<EdgeReads>();
+  merge_list_disconnected(e1, e2, offset1, *lf);
+  auto lr = std::make_unique<EdgeReads>();
+  merge_list_disconnected(e2r, e1r, offset2, *lr);
+  const uint64_t off_f = pool[e1].offset + pool[e2].offset + offset1;
+  const uint64_t off_r = pool[e1r].offset + pool[e2r].offset + offset2;
+  const uint32_t ef = new_edge(r1, r2, of, off_f, std::move(lf));
+  const uint32_t er = new_edge(r2, r1, orr, off_r, std::move(lr));
+  pool[ef].rev = er;
+  pool[er].rev = ef;
+  const uint16_t flow = std::min(pool[e1].flow, pool[e2].flow);
+  pool[ef].flow = flow;
+  pool[er].flow = flow;
+  insert(ef);
+  insert(er);
+  pool[e1].flow = (uint16_t)(pool[e1].flow - flow);
+  pool[pool[e1].rev].flow = pool[e1].flow;
+  pool[e2].flow = (uint16_t)(pool[e2].flow - flow);
+  pool[pool[e2].rev].flow = pool[e2].flow;
+  if (pool[e1].flow == 0 || flow == 0) remove(e1);
+  if (pool[e2].flow == 0 || flow == 0) remove(e2);
+}
+
 uint64_t UnitigGraph::contract_composite_paths() {  // :669-696
   uint64_t counter = 0;
   for (size_t index = 1; index < lists.size(); ++index) {

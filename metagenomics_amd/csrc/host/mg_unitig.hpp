@@ -69,6 +69,11 @@ class UnitigGraph {
   // mergeEdges (:702-753) of two pool entries, for findSupportByMatepairsAndMerge's
   // loop (mg_paths.cpp); sets bad_merge on an orientation pair it rejects
   void merge_edges(uint32_t e1, uint32_t e2) { merge(e1, e2); }
+  // the second part of mergeEdgesDisconnected (:2401-2467) for two pool entries
+  // that share no node (scaffolder's loop, mg_scaffold.cpp): offset1 / offset2 =
+  // overlapOffset1 / overlapOffset2 as :2412-2421 set them from findOverlap;
+  // sets bad_merge on an orientation above 3
+  void merge_edges_disconnected(uint32_t e1, uint32_t e2, uint64_t offset1, uint64_t offset2);
   // saveGraphToFile (:1219-1261); 0 ok, -1 open/write failure
   int save_unitig(const char* path) const;
   // every list in list order as "u v orient offset nreads r:o:d ..." rows,
@@ -92,6 +97,7 @@ class UnitigGraph {
   bool edge_present(uint32_t s, uint32_t d) const;
   void merge(uint32_t e1, uint32_t e2);
   void merge_list(uint32_t e1, uint32_t e2, EdgeReads& out) const;
+  void merge_list_disconnected(uint32_t e1, uint32_t e2, uint64_t overlap_offset, EdgeReads& out) const;
   void update_locations(uint32_t e);
   void remove_locations(uint32_t e);
   size_t list_size(uint32_t e) const { return reads[e] ? reads[e]->reads.size() : 0; }

@@ -32,6 +32,10 @@
 //                pairs, the three counters and their sums) and writes the graph
 //                after the merge to <prefix>.support.unitig (MG_DEVICE_PATHS=0 or no
 //                device: the search by the host mirror);
+//   -scaffold    main.cpp:59, then one scaffolder() (main.cpp:85): prints the
+//                reference's line per merged pair and writes the graph after the
+//                merge to <prefix>.scaffold.unitig (MG_DEVICE_SCAFFOLD=0 or no
+//                device: the scoring by the host mirror);
 //   -insert      main.cpp:59's calculateMeanAndSdOfInsertSize after the .unitig (also
 //                after -s), for use with -pe: per dataset the reference's three
 //                stdout lines ("Mean set to: ", "SD set to: ", "Reads on same
@@ -53,6 +57,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <iostream>
 #include <string>
 #include <thread>
 #include <vector>
@@ -328,9 +333,18 @@ static void save_support(OverlapGraph* g, size_t n_pe, const std::string& prefix
   g->saveGraphToFile(prefix + ".support.unitig");
 }
 
+// main.cpp:59, then one scaffolder() (main.cpp:85) with its lines, then the graph after the merge
+static void save_scaffold(OverlapGraph* g, const std::string& prefix) {
+  g->calculateMeanAndSdOfInsertSize();
+  std::fflush(stdout);
+  g->scaffolder();
+  std::cout << std::flush;
+  g->saveGraphToFile(prefix + ".scaffold.unitig");
+}
+
 static void usage() {
   std::fprintf(stderr,
-               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-contigs] [-insert] [-support] [-nocontract | -raw | -s | -xchg K "
+               "Usage: mg_overlap [-pe n f1..fn] [-se n f1..fn] -f prefix -l minOverlap [-k seedK] [-d device] [-mates] [-contigs] [-insert] [-support] [-scaffold] [-nocontract | -raw | -s | -xchg K "
                "[-xchg-sim P] [-xchg-caps F]]\n");
 }
 
@@ -339,7 +353,7 @@ int main(int argc, char** argv) {
   std::string prefix;
   unsigned long long l = 0;
   int k = 0, dev = 0;
-  bool raw = false, nocontract = false, resume = false, mates = false, contigs = false, insert = false, support = false;
+  bool raw = false, nocontract = false, resume = false, mates = false, contigs = false, insert = false, support = false, scaffold = false;
   int xchg_steps = -1, xchg_sim = 0;
   double xchg_caps = 1.0;
   for (int i = 1; i < argc; ++i) {
@@ -369,6 +383,8 @@ int main(int argc, char** argv) {
       insert = true;
     } else if (a == "-support") {
       support = true;
+    } else if (a == "-scaffold") {
+      scaffold = true;
     } else if (a == "-xchg" && i + 1 < argc) {
       xchg_steps = std::max(0, std::atoi(argv[++i]));
     } else if (a == "-xchg-sim" && i + 1 < argc) {
@@ -411,6 +427,7 @@ int main(int argc, char** argv) {
       if (contigs) save_contigs(g, ds, prefix);
       if (insert) save_insert(g, ds, pe.size(), prefix);
       if (support) save_support(g, pe.size(), prefix);
+      if (scaffold) save_scaffold(g, prefix);
       std::printf("{\"unique_reads\": %llu, \"nodes\": %llu, \"directed_edges\": %llu}\n",
                   (unsigned long long)ds->getNumberOfUniqueReads(), (unsigned long long)g->getNumberOfNodes(),
                   (unsigned long long)g->getNumberOfEdges());
@@ -433,6 +450,7 @@ int main(int argc, char** argv) {
       if (contigs) save_contigs(g, ds, prefix);
       if (insert) save_insert(g, ds, pe.size(), prefix);
       if (support) save_support(g, pe.size(), prefix);
+      if (scaffold) save_scaffold(g, prefix);
     }
     const mg_timings& t = g->timings();
     std::printf(

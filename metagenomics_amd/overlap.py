@@ -42,6 +42,10 @@ PAIR_DTYPE = np.dtype([("edge1", "<u4"), ("edge2", "<u4"), ("support", "<u8")])
 PATH_SKIPPED, PATH_SAME_EDGE, PATH_NONE, PATH_FOUND, PATH_DEFERRED = range(5)
 # the reference's minimumSupport (Common.h:43)
 MIN_SUPPORT = 3
+# one edge pair the scaffolder's mate entries support (mg_scaffold_pair, include/mg_overlap.h): 24 bytes
+SCAFFOLD_PAIR_DTYPE = np.dtype([("edge1", "<u4"), ("edge2", "<u4"), ("support", "<u8"), ("distance", "<u8")])
+# status of a mate entry in the scaffolder's scoring (MG_SCAF_*, include/mg_overlap.h)
+SCAF_SKIPPED, SCAF_NOT_UNIQUE, SCAF_FAR, SCAF_SAME_EDGE, SCAF_COUNTED = range(5)
 # one half-edge of a replayed graph's CSR (mg_chain_edge, include/mg_overlap.h): 12 bytes
 CHAIN_EDGE_DTYPE = np.dtype([("dst", "<u4"), ("twin", "<u4"), ("offset", "<u2"), ("orient", "u1"), ("pad", "u1")])
 # one safe chain (mg_chain, include/mg_overlap.h): 48 bytes
@@ -212,6 +216,13 @@ def lib() -> C.CDLL:
         "mgh_mate_paths": (i32, [u64, vp, vp, u64, vp, vp, vp, vp, vp, vp, u32, u64, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                  vp, u64, P(u64), vp, u64, P(u64), vp, C.c_char_p, u64]),
         "mgh_graph_merge_supported": (i32, [vp, vp, u64, u64, P(u64), C.c_char_p, u64]),
+        "mg_scaffold_pairs": (i32, [vp, vp, u64, u64, vp, vp, vp, vp, vp, vp, u32, vp, P(u64), P(C.c_float)]),
+        "mg_copy_scaffold_entries": (i32, [vp, vp]),
+        "mg_copy_scaffold_pairs": (i32, [vp, vp, u64, P(u64)]),
+        "mg_scaffold_info": (i32, [vp, vp, vp]),
+        "mgh_scaffold_pairs": (i32, [u64, vp, u64, vp, vp, vp, vp, vp, vp, u32, vp, vp, u64, P(u64), vp, C.c_char_p,
+                                     u64]),
+        "mgh_graph_merge_scaffold": (i32, [vp, vp, u64, u64, vp, vp, u64, u32, vp, u64, P(u64), P(u64), C.c_char_p, u64]),
         "mg_build_chains": (i32, [vp, vp, vp, u64, u64, P(u64), P(u64), vp, P(C.c_float)]),
         "mg_copy_chains": (i32, [vp, vp, u64, vp, vp, vp, u64]),
         "mgh_graph_simple_csr": (u64, [vp, vp, vp, u64]),
@@ -728,6 +739,52 @@ class OverlapEngine:
                            (n_reads, edges, twin, places if places is not None else self.placements,
                             mates if mates is not None else self.mate_lists, mean, sd))
 
+    # --- scaffolder support
+    def scaffold_pairs(self, twin, n_edges: int, mean, sd, places=None, mates=None,
+                       n_reads: int | None = None) -> "ScaffoldSupport":
+        """mg_scaffold_pairs: the scoring half of OverlapGraph::scaffolder
+        (OverlapGraph.cpp:2120-2195) on the device.  twin as
+        UnitigGraph.edge_twins gives it (n_edges entries); places = a (start,
+        records) placement CSR, or None: the resident placements of
+        build_placements (identical results: only lists of one placement are
+        read); mates = a (start, records) mate CSR, or None: the resident lists;
+        mean / sd per dataset.  scaffold_ms = (score kernel, aggregate) device
+        time."""
+        twin = np.ascontiguousarray(twin, dtype=np.uint32)
+        mean = np.ascontiguousarray(mean, dtype=np.uint64)
+        sd = np.ascontiguousarray(sd, dtype=np.uint64)
+        if twin.shape[0] != n_edges or mean.shape != sd.shape or mean.ndim != 1:
+            raise MgError("scaffold_pairs: one twin per edge, one mean and one sd per dataset")
+        if places is not None:
+            places = (np.ascontiguousarray(places[0], dtype=np.uint64), np.ascontiguousarray(places[1], dtype=PLACE_DTYPE))
+        if mates is not None:
+            mates = (np.ascontiguousarray(mates[0], dtype=np.uint64), np.ascontiguousarray(mates[1], dtype=MATE_DTYPE))
+        if n_reads is None:
+            n_reads = (places[0].shape[0] - 2 if places is not None else
+                       mates[0].shape[0] - 2 if mates is not None else int(lib().mg_num_reads(self._h)))
+        for csr in (places, mates):
+            if csr is not None and (csr[0].shape[0] != n_reads + 2 or int(csr[0][-1]) > csr[1].shape[0]):
+                raise MgError("scaffold_pairs: a CSR does not fit n_reads")
+        counters = np.zeros(5, dtype=np.uint64)
+        npairs, ms = C.c_uint64(), C.c_float()
+        self._check(lib().mg_scaffold_pairs(self._h, _ptr(twin), n_edges, n_reads,
+                                            None if places is None else _ptr(places[0]),
+                                            None if places is None else _ptr(places[1]),
+                                            None if mates is None else _ptr(mates[0]),
+                                            None if mates is None else _ptr(mates[1]), _ptr(mean), _ptr(sd),
+                                            mean.shape[0], _ptr(counters), C.byref(npairs), C.byref(ms)),
+                    "scaffold_pairs")
+        info, times = np.zeros(3, dtype=np.uint64), np.zeros(2, dtype=np.float32)
+        self._check(lib().mg_scaffold_info(self._h, _ptr(info), _ptr(times)), "scaffold_info")
+        self.scaffold_ms = (float(times[0]), float(times[1]))
+        status = np.zeros(int(info[0]), dtype=np.uint8)
+        self._check(lib().mg_copy_scaffold_entries(self._h, _ptr(status)), "copy_scaffold_entries")
+        pairs = np.zeros(npairs.value, dtype=SCAFFOLD_PAIR_DTYPE)
+        got = C.c_uint64()
+        self._check(lib().mg_copy_scaffold_pairs(self._h, _ptr(pairs), pairs.shape[0], C.byref(got)),
+                    "copy_scaffold_pairs")
+        return ScaffoldSupport(status, pairs[: got.value], counters)
+
     # --- connected components of the lists, labelled on the device
     def build_components(self) -> int:
         """mg_build_components: label every read with the smallest read ID its
@@ -1217,6 +1274,43 @@ def host_mate_paths(n_reads: int, edges, twin, places, mates, mean, sd, budget: 
                        int((status == PATH_DEFERRED).sum()), (n_reads, edges, twin, (pstart, precs), (mstart, mrecs), mean, sd))
 
 
+class ScaffoldSupport:
+    """What scaffold_pairs / host_scaffold_pairs return: status[t] (SCAF_*) per
+    mate entry in (A, j) order; pairs[SCAFFOLD_PAIR_DTYPE] in first-seen order
+    (listOfPairedEdges before its sort; distance = the sum over the record's
+    entries); counters = the entries of each status, indexed by SCAF_*."""
+
+    def __init__(self, status, pairs, counters):
+        self.status, self.pairs = status, pairs
+        self.counters = tuple(int(x) for x in counters)
+
+
+def host_scaffold_pairs(n_reads: int, twin, places, mates, mean, sd) -> ScaffoldSupport:
+    """mg::scaffold_pairs (mgh_scaffold_pairs): the host mirror of
+    OverlapEngine.scaffold_pairs over the same arrays; places / mates = (start,
+    records) CSRs."""
+    twin = np.ascontiguousarray(twin, dtype=np.uint32)
+    pstart, precs = np.ascontiguousarray(places[0], dtype=np.uint64), np.ascontiguousarray(places[1], dtype=PLACE_DTYPE)
+    mstart, mrecs = np.ascontiguousarray(mates[0], dtype=np.uint64), np.ascontiguousarray(mates[1], dtype=MATE_DTYPE)
+    mean = np.ascontiguousarray(mean, dtype=np.uint64)
+    sd = np.ascontiguousarray(sd, dtype=np.uint64)
+    if mean.shape != sd.shape or mean.ndim != 1 or pstart.shape[0] != n_reads + 2 or mstart.shape[0] != n_reads + 2 or \
+            int(pstart[-1]) > precs.shape[0] or int(mstart[-1]) > mrecs.shape[0]:
+        raise MgError("host_scaffold_pairs: the arrays do not fit each other")
+    m = int(mstart[-1])
+    status = np.zeros(m, dtype=np.uint8)
+    pairs = np.zeros(m, dtype=SCAFFOLD_PAIR_DTYPE)  # (every record holds at least one entry)
+    counters = np.zeros(5, dtype=np.uint64)
+    npairs = C.c_uint64()
+    err = C.create_string_buffer(512)
+    rc = lib().mgh_scaffold_pairs(n_reads, _ptr(twin), twin.shape[0], _ptr(pstart), _ptr(precs), _ptr(mstart),
+                                  _ptr(mrecs), _ptr(mean), _ptr(sd), mean.shape[0], _ptr(status), _ptr(pairs), m,
+                                  C.byref(npairs), _ptr(counters), err, 512)
+    if rc:
+        raise MgError(f"host_scaffold_pairs: {err.value.decode() or 'bad arguments'} ({rc})")
+    return ScaffoldSupport(status, pairs[: npairs.value], counters)
+
+
 def read_pairs(files: Sequence[str] | None = None, data: bytes | None = None):
     """The mates of every pair as storeMatePairInformation's loop reads them
     (mgh_read_pairs; `data`: one file's bytes).  Returns (text bytes, offsets
@@ -1524,6 +1618,41 @@ class UnitigGraph:
         if engine is not None:
             return engine.mate_paths(edges, twin, mean, sd, places=locs, mates=mates).finish()
         return host_mate_paths(locs[0].shape[0] - 2, edges, twin, locs, mates, mean, sd)
+
+    def scaffold_support(self, mates, mean, sd, engine=None) -> "ScaffoldSupport":
+        """The scoring half of scaffolder() (OverlapGraph.cpp:2120-2195) over
+        this graph: statuses, records and counters (ScaffoldSupport).  mates = a
+        (start, records) mate CSR; mean / sd per dataset (insert_sizes).  With
+        an engine: the device call; otherwise the host mirror."""
+        locs = self.location_lists()
+        if locs is None:
+            raise MgError("scaffold_support: the graph tracked no read locations")
+        twin = self.edge_twins()
+        if engine is not None:
+            return engine.scaffold_pairs(twin, twin.shape[0], mean, sd, places=locs, mates=mates)
+        return host_scaffold_pairs(locs[0].shape[0] - 2, twin, locs, mates, mean, sd)
+
+    def merge_scaffold(self, pairs, words, lens, min_support: int = MIN_SUPPORT):
+        """The merging half of scaffolder() (OverlapGraph.cpp:2197-2219): std::sort
+        of the records by support, then, for every record no earlier merge freed
+        with support >= min_support, the reference's "are supported" line and
+        mergeEdgesDisconnected.  pairs[SCAFFOLD_PAIR_DTYPE] index
+        contig_edges(all_edges=True) of the graph as it is now; words / lens =
+        the packed reads in ID order (Dataset.packed()).  Returns
+        (pairsOfEdgesMerged, the lines as one string)."""
+        pairs = np.ascontiguousarray(pairs, dtype=SCAFFOLD_PAIR_DTYPE)
+        words = np.ascontiguousarray(words, dtype=np.uint64)
+        lens = np.ascontiguousarray(lens, dtype=np.uint16)
+        wpr = words.shape[1] if words.ndim == 2 else 1
+        merged, used = C.c_uint64(), C.c_uint64()
+        err = C.create_string_buffer(512)
+        cap = 192 * pairs.shape[0] + 1
+        lines = C.create_string_buffer(cap)
+        rc = self._L.mgh_graph_merge_scaffold(self._g, _ptr(pairs), pairs.shape[0], min_support, _ptr(words), _ptr(lens),
+                                              lens.shape[0], wpr, lines, cap, C.byref(used), C.byref(merged), err, 512)
+        if rc:
+            raise MgError(f"merge_scaffold: {err.value.decode() or 'bad arguments'} ({rc})")
+        return int(merged.value), lines.raw[: used.value].decode()
 
     def merge_supported(self, pairs, min_support: int = MIN_SUPPORT) -> int:
         """The merging half (OverlapGraph.cpp:1968-1992): std::sort of the pairs
